@@ -14,7 +14,7 @@ three launches last ~0.3 ms under load): with the driver's K = 20 the headline i
 
 Multi-GPU (launched by torch.distributed.run, one rank per GPU; "nccl" = RCCL over xGMI).  Independent registrations
 shard with no data-path collective; the only collectives are the set-up broadcast of the submap tables and the result
-gather.  Two regions are timed at N > 1:
+gather.  Two regions are timed at N > 1 (the strong one only with --full or --scaling strong):
   * weak   (the headline `value`): every rank processes its own 512-registration batch per step;
   * strong (`strong_scaling`): BASELINE config 4 as written -- ONE batch of 512 (seeds 1000..1511) split contiguously,
     rank r runs [r*512/N, (r+1)*512/N), results all-gathered and checked bit-identical to the unsharded batch.
@@ -24,6 +24,16 @@ Roofline: this path is not HBM-bound (counter traffic is ~10x below the dense-ta
 against the VALU issue rate: counted instructions per launch (rocprofv3 SQ counters, profiles/*_sq_summary.csv) x
 measured issue cycles per instruction class (tools/valu_rate_probe.hip) / the launch duration measured here with HIP
 events, over 1024 SIMDs x 2.4 GHz.  The SURVEY byte model and the counter traffic are kept as labelled secondaries.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, warm-up (W steps per
+stream, the settle region, then up to 8 untimed K-step regions within about a second; none of it reported), ONE region of
+exactly K timed steps, and the line.  --full adds
+everything else: `sustained`, the --repeats median (9 regions), the strong / pipelined multi-GPU regions, `hbm_achieved`,
+the roofline sections, the CPU baselines and the side measurements of the other BASELINE configs.
+
+--dump-outputs DIR writes what the timed path returned in its last step, as float64 .npy files: `pose.npy` (B x 4, the
+solved poses as cos, sin, x, y) and `result_<field>.npy` (B, one per field of the 64-byte result record).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -157,6 +167,24 @@ def hbm_achieved(counters, ms_per_step, sustained_ms_per_step, counters_file, co
     return out
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def write_outputs(dirname, pose, records):
+    """--dump-outputs: the poses (B x 4) and result records (B) of the timed path's last step, as float64 .npy files.  Above
+    DUMP_BYTES_MAX in all (only at a large --batch-scale) a fixed seeded sample of the rows is written, its indices in rows.npy."""
+    fields = [f for f in records.dtype.names if f != "reserved"]
+    n_max = DUMP_BYTES_MAX // (8 * (pose.shape[1] + len(fields) + 1))
+    os.makedirs(dirname, exist_ok=True)
+    rows = slice(None)
+    if len(pose) > n_max:
+        rows = np.sort(np.random.default_rng(0).choice(len(pose), n_max, replace=False))
+        np.save(os.path.join(dirname, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, "pose.npy"), np.asarray(pose[rows], dtype=np.float64))
+    for f in fields:
+        np.save(os.path.join(dirname, "result_%s.npy" % f), records[f][rows].astype(np.float64))
+
+
 class GroupBatch:
     """BASELINE config 4 as written -- ONE batch split over the GPUs of the node -- through the C ABI's multi-GPU group
     (randt_group_scan_register_batch_dev): every rank holds the full input arrays, runs its contiguous shard (NDT build ->
@@ -232,7 +260,8 @@ EVENT_EVERY = 67
 
 def timed_region(torch, dist, world, dev, batch, streams, n_steps, only=None):
     """EXACTLY n_steps steps between barrier + synchronize on both sides; MAX over ranks.  The initial guess is an input
-    and the solve updates it in place (Sophus::SE2d& trans): every step gets its own copy, resident beforehand."""
+    and the solve updates it in place (Sophus::SE2d& trans): every step gets its own copy, resident beforehand; the
+    last step's is returned."""
     n_streams = len(streams)
     step_pose = [batch.guess4.clone() for _ in range(n_steps)]
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] if s % EVENT_EVERY == EVENT_EVERY // 2 or n_steps <= EVENT_EVERY and s == n_steps // 2
@@ -255,7 +284,7 @@ def timed_region(torch, dist, world, dev, batch, streams, n_steps, only=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     stage_ms = np.array([[ev[s][i].elapsed_time(ev[s][i + 1]) for i in range(3)] for s in range(n_steps) if ev[s] is not None] or [[0.0] * 3]).mean(axis=0)
-    return elapsed, t_enq, stage_ms, step_pose[0]
+    return elapsed, t_enq, stage_ms, step_pose[-1]
 
 
 def warm_up(torch, batch, streams, n):
@@ -276,7 +305,13 @@ def main():
     ap.add_argument("--steps", type=int, default=1000, help="steps of the timed region (exactly this many)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--min-seconds", type=float, default=0.3, help="length of the untimed settle region in front of the timed one (clocked on the side: `sustained`)")
-    ap.add_argument("--repeats", type=int, default=9, help="the exact --steps region is run this many times (median reported, all listed)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the exact --steps region is run this many times (median reported, all listed); default 9 with --full, else 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: sustained rate, repeats, strong scaling, roofline, CPU baselines and "
+                         "the side measurements of the other configs (their options below only act with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the poses and result records of the timed path's last step to DIR/*.npy (float64)")
     ap.add_argument("--scaling", choices=["weak", "strong", "both"], default="both",
                     help="multi-GPU regions to time (the headline value is the weak one unless only strong is asked for)")
     ap.add_argument("--batch-scale", type=int, default=1,
@@ -304,11 +339,13 @@ def main():
     ap.add_argument("--event-every", type=int, default=EVENT_EVERY, help="bracket the launches of every N-th timed step with HIP events (stage residency)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--force-group-path", action="store_true",
-                    help="test hook: run the multi-GPU code path (randt_group over RCCL, strong regions) with ONE rank on one GPU")
+                    help="test hook: run the multi-GPU code path (randt_group over RCCL; strong regions with --full) with ONE rank on one GPU")
     ap.add_argument("--no-config2", action="store_true", help="skip the single-pair latency section (BASELINE config 2)")
     ap.add_argument("--no-roofline-sections", action="store_true", help="skip the single-stream / chip-filling-launch sections")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="wall-clock budget of each CPU baseline leg")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
 
     globals()["EVENT_EVERY"] = max(1, args.event_every)
     # in-flight batches need their own hardware queues to overlap (must be set before the HIP runtime starts)
@@ -347,6 +384,8 @@ def main():
             dist.init_process_group(backend=backend)
     via_cpu = world > 1 and backend != "nccl"
     multi = world > 1 or args.force_group_path   # --force-group-path: the multi-GPU code (groups, strong regions, JSON keys) on ONE rank
+    # the strong regions are the headline only under --scaling strong; with the default "both" they are a --full figure
+    run_strong = multi and (args.scaling == "strong" or (args.full and args.scaling == "both"))
 
     # One randt context per HIP stream: consecutive steps (independent batches) alternate streams so
     # that the latency-bound tail of one batch's solve overlaps the next batch's build / association.
@@ -436,7 +475,7 @@ def main():
             grp, submaps_g, group_error = make_group(streams[0])
             if grp is None:
                 sys.stderr.write("rank %d: falling back to torch.distributed for the exchanges\n" % rank)
-            else:
+            elif run_strong:
                 # further groups (own communicator, own stream): several split batches in flight for the pipelined strong region
                 for j in range(1, max(1, min(int(os.environ.get("RANDT_BENCH_STRONG_GROUPS", "4")), n_streams))):
                     g2, sm2, e2 = make_group(streams[j])
@@ -478,9 +517,10 @@ def main():
 
     # ---------------- timed region (weak = the headline) --------------------------------------------
     # settle (untimed for the headline, clocked on the side), then EXACTLY args.steps steps, args.repeats times; `elapsed` is
-    # already the maximum over ranks, so every rank takes the same decisions
+    # already the maximum over ranks, so every rank takes the same decisions.  Without --full the settle region is warm-up
+    # only and does not grow with --steps, so that a long timed region is not paid for twice.
     def settle(batch, use_streams=None):
-        n, best = max(args.steps, 16 * n_streams), None
+        n, best = max(args.steps if args.full else 0, 16 * n_streams), None
         if args.min_seconds <= 0:
             return None
         for _ in range(6):
@@ -493,11 +533,19 @@ def main():
 
     def region(batch, use_streams=None):
         sus = settle(batch, use_streams)
-        runs = [timed_region(torch, dist, world, dev, batch, use_streams or streams, args.steps, args.only) for _ in range(max(1, args.repeats))]
+        if not args.full and sus is not None:
+            # the first K-step regions after the settle run slower (K = 20: 2.0 ms, then down to 1.7 ms by the 8th), which the
+            # --full median of 9 never reports: up to 8 identical regions run untimed first, while they fit in about a second
+            est, spent = args.steps * sus[1] / sus[0], 0.0
+            for _ in range(8):
+                if spent + est > 1.0:
+                    break
+                spent += timed_region(torch, dist, world, dev, batch, use_streams or streams, args.steps, args.only)[0]
+        runs =[timed_region(torch, dist, world, dev, batch, use_streams or streams, args.steps, args.only) for _ in range(max(1, args.repeats))]
         order = sorted(range(len(runs)), key=lambda i: runs[i][0])
         r = runs[order[len(order) // 2]]
         info = {"repeats": len(runs), "region_ms": [x[0] * 1e3 for x in runs]}
-        if sus is not None:
+        if sus is not None and args.full:
             info["sustained"] = {"steps": sus[0], "timed_region_s": sus[1], "ms_per_step": sus[1] / sus[0] * 1e3,
                                  "value": batch.B * sus[0] * (world if batch is full else 1) / sus[1], "unit": "registrations/s",
                                  "stage_ms": [float(v) for v in sus[3]],
@@ -507,19 +555,21 @@ def main():
 
     out = {}
     if args.scaling != "strong" or world == 1:
-        n_steps, elapsed, t_enqueued, stage_ms, pose0, rinfo = region(full)
+        n_steps, elapsed, t_enqueued, stage_ms, last_pose, rinfo = region(full)
         value = B * n_steps * world / elapsed
         scaling = "weak"
+        if args.dump_outputs:   # copied now: the --full sections below reuse the batch's buffers
+            dump = (last_pose.cpu(), full.results[(n_steps - 1) % n_streams].cpu())
     strong = None
-    if multi and args.scaling in ("strong", "both"):
+    if run_strong:
         lo, hi = shard.shard_range(B, world, rank)
         extra = {}
         if grp is not None:
             # through the C ABI: shard + kernels + ONE RCCL exchange of the packed (pose, record) rows inside every step
             part = GroupBatch(R, torch, [grp], [submaps_g], mapp, clu, mp, *to_dev(base))
             warm_up(torch, part, streams[:1], 4)
-            s_steps, s_elapsed, s_enq, s_stage, s_pose0, s_info = region(part, streams[:1])
-            all_pose, all_res, t_gather = s_pose0, part.results[0], None
+            s_steps, s_elapsed, s_enq, s_stage, s_last_pose, s_info = region(part, streams[:1])
+            all_pose, all_res, t_gather = s_last_pose, part.results[0], None
             how = "randt_group_scan_register_batch_dev (C ABI, one ncclAllGather of packed 96-byte rows inside every step, one stream)"
             # the same region without the exchange: what the kernels alone cost per step
             nog = GroupBatch(R, torch, [grp], [submaps_g], mapp, clu, mp, *to_dev(base), gather=False)
@@ -541,11 +591,11 @@ def main():
         else:
             part = Batch(R, torch, ctxs, submaps_v, mapp, clu, mp, *to_dev(base, lo, hi))
             warm_up(torch, part, streams, 2 * n_streams)
-            s_steps, s_elapsed, s_enq, s_stage, s_pose0, s_info = region(part)
+            s_steps, s_elapsed, s_enq, s_stage, s_last_pose, s_info = region(part)
             # result gather (all-gather of 32-B poses + 64-B records) and the bit-identity check against the unsharded batch
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            lp, lr = (s_pose0.cpu(), part.results[0].cpu()) if via_cpu else (s_pose0, part.results[0])
+            lp, lr = (s_last_pose.cpu(), part.results[0].cpu()) if via_cpu else (s_last_pose, part.results[0])
             all_pose = shard.gather_results(lp)
             all_res = shard.gather_results(lr)
             torch.cuda.synchronize()
@@ -573,14 +623,14 @@ def main():
             strong["poses_bit_identical_to_unsharded"] = bool(torch.equal(all_pose.cpu(), rp.cpu()) and
                                                               torch.equal(all_res.cpu(), ref.results[0].cpu()))
         if args.scaling == "strong":
-            n_steps, elapsed, t_enqueued, stage_ms, pose0, value, scaling, rinfo = s_steps, s_elapsed, s_enq, s_stage, s_pose0, strong["value"], "strong", s_info
+            n_steps, elapsed, t_enqueued, stage_ms, last_pose, value, scaling, rinfo = s_steps, s_elapsed, s_enq, s_stage, s_last_pose, strong["value"], "strong", s_info
+            if args.dump_outputs:
+                dump = (all_pose.cpu(), all_res.cpu())
 
     if rank == 0:
         res = full.results[0].cpu().numpy().view(R.RESULT_DTYPE).reshape(-1)
         m_mean = float(full.scan_maps[0].counts().mean())
         n_res_mean = float(res["n_residuals"].mean())
-        b_alg = algorithmic_bytes(N_POINTS, N_SLOTS, m_mean, k)
-        counters, counters_file, counters_stale = load_counters()
         out = {
             "metric": "ndt_registrations_per_sec" if args.only is None and args.batch_scale == 1 else "DIAGNOSTIC_only=%s_batch_scale=%d" % (args.only, args.batch_scale),
             "value": value, "unit": "registrations/s",
@@ -599,15 +649,11 @@ def main():
             },
             "repeats": rinfo["repeats"], "region_ms": rinfo["region_ms"],
             "region_note": "value = batch x steps / the MEDIAN of `repeats` regions of exactly `steps` steps, each between barrier + synchronize "
-                           "(fill and drain of the 16-stream pipeline included: a burst figure at small --steps); `sustained` = the settle region",
+                           "(fill and drain of the 16-stream pipeline included: a burst figure at small --steps); `sustained` (--full) = the settle region",
             "host_enqueue_ms_per_step": t_enqueued / n_steps * 1e3,
             "stage_ms": {"ndt_build": float(stage_ms[0]), "associate": float(stage_ms[1]), "solve": float(stage_ms[2]),
                          "note": "HIP-event residency of each launch while %d batches share the chip (not a per-step cost)" % n_streams},
         }
-        if "sustained" in rinfo:
-            out["sustained"] = rinfo["sustained"]
-        out["hbm_achieved"] = hbm_achieved(counters, elapsed / n_steps * 1e3, rinfo["sustained"]["ms_per_step"] if "sustained" in rinfo else None,
-                                           counters_file, counters_stale)
         if multi:
             # LOUD: a first-ever RCCL failure on a multi-GPU node must not look like a pass
             out["group_fallback"] = bool(grp is None and not via_cpu)
@@ -618,85 +664,94 @@ def main():
                 out["ranks_share_one_gpu"] = True   # a test of the RCCL path (socket transport between fake nodes), NOT a scaling figure
         if strong is not None:
             out["strong_scaling"] = strong
-        # Everything below is a side measurement on rank 0: a failure there must never cost the headline line.
-        def side(key, fn, *a):
-            try:
-                r = fn(*a)
-                if key is None:
-                    out.update(r)
-                else:
-                    out[key] = r
-            except Exception as e:  # noqa: BLE001 -- reported in the line, not raised
-                out[key or "side_measurement_error"] = {"error": "%s: %s" % (type(e).__name__, e)}
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, dump[0].numpy(), dump[1].numpy().view(R.RESULT_DTYPE).reshape(-1))
+        if args.full:
+            b_alg = algorithmic_bytes(N_POINTS, N_SLOTS, m_mean, k)
+            counters, counters_file, counters_stale = load_counters()
+            if "sustained" in rinfo:
+                out["sustained"] = rinfo["sustained"]
+            out["hbm_achieved"] = hbm_achieved(counters, elapsed / n_steps * 1e3, rinfo["sustained"]["ms_per_step"] if "sustained" in rinfo else None,
+                                               counters_file, counters_stale)
+            # Everything below is a side measurement on rank 0: a failure there must never cost the headline line.
+            def side(key, fn, *a):
+                try:
+                    r = fn(*a)
+                    if key is None:
+                        out.update(r)
+                    else:
+                        out[key] = r
+                except Exception as e:  # noqa: BLE001 -- reported in the line, not raised
+                    out[key or "side_measurement_error"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-        if not args.no_roofline_sections and args.only is None and args.batch_scale == 1:
-            # (at N > 1 too: rank 0 alone, the other ranks wait at the closing barrier; per-GPU figures)
-            side(None, roofline_sections, R, torch, full, streams, ctxs, submaps_v, mapp, clu, mp, counters, counters_file,
-                 b_alg, (rinfo["sustained"]["value"] if "sustained" in rinfo else value) / world,
-                 (rinfo["sustained"]["ms_per_step"] * 1e-3 if "sustained" in rinfo else elapsed / n_steps), counters_stale, throughput_mode,
-                 elapsed / n_steps)
-        if world == 1 and args.only is None and args.batch_scale == 1 and args.distinct_inputs > 1:
-            def distinct_region():
-                # the headline once more with the point batches at DISTINCT addresses: step s reads copy s % n of the 512 scans
-                # (n x 16.4 MB > the 256 MB Infinity Cache: no step meets its input again in a cache); the working sets of the 16
-                # streams (scan cell tables, correspondences: 265 MB) were distinct all along
-                n = args.distinct_inputs
-                full.points_rotation = [full.points] + [full.points.clone() for _ in range(n - 1)]
-                try:
-                    warm_up(torch, full, streams, 2 * n_streams)
-                    d_steps, d_elapsed, _, _, d_pose0, d_info = region(full)
-                finally:
-                    full.points_rotation = None
-                r = {"copies": n, "input_bytes": int(n * full.points.numel() * 4), "steps": d_steps, "ms_per_step": d_elapsed / d_steps * 1e3,
-                     "value": B * d_steps / d_elapsed, "unit": "registrations/s", "region_ms": d_info["region_ms"],
-                     "poses_equal_headline": bool(torch.equal(d_pose0, pose0)),
-                     "note": "same values at other addresses: identical results, nothing re-read from the Infinity Cache"}
-                if "sustained" in d_info:
-                    r["sustained"] = {k: d_info["sustained"][k] for k in ("steps", "ms_per_step", "value")}
-                return r
-            side("distinct_inputs", distinct_region)
-        if world == 1 and args.only is None and args.batch_scale == 1 and throughput_mode and n_streams > 1 and not args.no_auto_region:
-            def auto_region():
-                # the headline region with every context left in RANDT_SOLVE_AUTO: the library itself has to notice that 16 contexts
-                # keep batches in flight (enqueue stamps / hipStreamQuery) and take the throughput placement -- same rate, same poses
-                for c in ctxs:
-                    c.set_solve_mode(R._capi.SOLVE_AUTO)
-                try:
-                    warm_up(torch, full, streams, 2 * n_streams)
-                    a_steps, a_elapsed, _, _, a_pose0, a_info = region(full)
-                finally:
+            if not args.no_roofline_sections and args.only is None and args.batch_scale == 1:
+                # (at N > 1 too: rank 0 alone, the other ranks wait at the closing barrier; per-GPU figures)
+                side(None, roofline_sections, R, torch, full, streams, ctxs, submaps_v, mapp, clu, mp, counters, counters_file,
+                     b_alg, (rinfo["sustained"]["value"] if "sustained" in rinfo else value) / world,
+                     (rinfo["sustained"]["ms_per_step"] * 1e-3 if "sustained" in rinfo else elapsed / n_steps), counters_stale, throughput_mode,
+                     elapsed / n_steps)
+            if world == 1 and args.only is None and args.batch_scale == 1 and args.distinct_inputs > 1:
+                def distinct_region():
+                    # the headline once more with the point batches at DISTINCT addresses: step s reads copy s % n of the 512 scans
+                    # (n x 16.4 MB > the 256 MB Infinity Cache: no step meets its input again in a cache); the working sets of the 16
+                    # streams (scan cell tables, correspondences: 265 MB) were distinct all along
+                    n = args.distinct_inputs
+                    full.points_rotation = [full.points] + [full.points.clone() for _ in range(n - 1)]
+                    try:
+                        warm_up(torch, full, streams, 2 * n_streams)
+                        d_steps, d_elapsed, _, _, d_last_pose, d_info = region(full)
+                    finally:
+                        full.points_rotation = None
+                    r = {"copies": n, "input_bytes": int(n * full.points.numel() * 4), "steps": d_steps, "ms_per_step": d_elapsed / d_steps * 1e3,
+                         "value": B * d_steps / d_elapsed, "unit": "registrations/s", "region_ms": d_info["region_ms"],
+                         "poses_equal_headline": bool(torch.equal(d_last_pose, last_pose)),
+                         "note": "same values at other addresses: identical results, nothing re-read from the Infinity Cache"}
+                    if "sustained" in d_info:
+                        r["sustained"] = {k: d_info["sustained"][k] for k in ("steps", "ms_per_step", "value")}
+                    return r
+                side("distinct_inputs", distinct_region)
+            if world == 1 and args.only is None and args.batch_scale == 1 and throughput_mode and n_streams > 1 and not args.no_auto_region:
+                def auto_region():
+                    # the headline region with every context left in RANDT_SOLVE_AUTO: the library itself has to notice that 16 contexts
+                    # keep batches in flight (enqueue stamps / hipStreamQuery) and take the throughput placement -- same rate, same poses
                     for c in ctxs:
-                        c.set_solve_mode(R._capi.SOLVE_THROUGHPUT)
-                r = {"value": B * a_steps / a_elapsed, "unit": "registrations/s", "ms_per_step": a_elapsed / a_steps * 1e3,
-                     "vs_explicit_throughput_mode": (B * a_steps / a_elapsed) / value, "poses_equal_headline": bool(torch.equal(a_pose0, pose0))}
-                if "sustained" in a_info:
-                    r["sustained"] = {k: a_info["sustained"][k] for k in ("steps", "ms_per_step", "value")}
-                    if "sustained" in rinfo:
-                        r["sustained"]["vs_explicit_throughput_mode"] = a_info["sustained"]["value"] / rinfo["sustained"]["value"]
-                return r
-            side("solve_auto_detection", auto_region)
-        if not args.no_cpu_baseline and world == 1:
-            side(None, cpu_baseline, weak_prob, mp, pose0.cpu().numpy(), args.cpu_seconds)
-        if world == 1 and args.only is None and not args.no_config2:
-            side("config2_single_pair", config2_single_pair, R, torch, ctx, submaps, full, mapp, clu, mp, weak_prob, not args.no_cpu_baseline,
-                 min(3.0, args.cpu_seconds))
-            if throughput_mode:
-                ctx.set_solve_mode(R._capi.SOLVE_THROUGHPUT)
-        if world == 1 and args.only is None and not args.no_config2:
-            side("loop_gate_and_search", loop_gate_and_search, R, torch, ctx, submaps, full, mp, weak_prob, not args.no_cpu_baseline, min(2.0, args.cpu_seconds))
-        if args.odometry_scans > 0 and world == 1:
-            side("config3_streaming_odometry", streaming_odometry, ctx, args.odometry_scans, not args.no_cpu_baseline)
-        if args.replica_steps > 0 and world == 1:
-            side("config3_replicas", config3_replicas, ctx, args.replica_steps)
-        if args.cpp_drive_scans > 0 and world == 1:
-            py = out.get("config3_streaming_odometry", {})
-            side("cpp_local_fuser_drive", cpp_local_fuser_drive, ctx, args.cpp_drive_scans, py.get("ms_per_scan") if isinstance(py, dict) else None)
-        if args.polar_scans > 0 and world == 1:
-            side("config5_polar_filter", polar_filter, ctx, args.polar_scans)
-        if args.slam_scans > 0 and world == 1:
-            side("slam_loop", slam_loop, ctx, args.slam_scans)
-        if args.polar_odometry_scans > 0 and world == 1:
-            side("config5_polar_odometry", polar_odometry, ctx, args.polar_odometry_scans)
+                        c.set_solve_mode(R._capi.SOLVE_AUTO)
+                    try:
+                        warm_up(torch, full, streams, 2 * n_streams)
+                        a_steps, a_elapsed, _, _, a_last_pose, a_info = region(full)
+                    finally:
+                        for c in ctxs:
+                            c.set_solve_mode(R._capi.SOLVE_THROUGHPUT)
+                    r = {"value": B * a_steps / a_elapsed, "unit": "registrations/s", "ms_per_step": a_elapsed / a_steps * 1e3,
+                         "vs_explicit_throughput_mode": (B * a_steps / a_elapsed) / value, "poses_equal_headline": bool(torch.equal(a_last_pose, last_pose))}
+                    if "sustained" in a_info:
+                        r["sustained"] = {k: a_info["sustained"][k] for k in ("steps", "ms_per_step", "value")}
+                        if "sustained" in rinfo:
+                            r["sustained"]["vs_explicit_throughput_mode"] = a_info["sustained"]["value"] / rinfo["sustained"]["value"]
+                    return r
+                side("solve_auto_detection", auto_region)
+            if not args.no_cpu_baseline and world == 1:
+                side(None, cpu_baseline, weak_prob, mp, last_pose.cpu().numpy(), args.cpu_seconds)
+            if world == 1 and args.only is None and not args.no_config2:
+                side("config2_single_pair", config2_single_pair, R, torch, ctx, submaps, full, mapp, clu, mp, weak_prob, not args.no_cpu_baseline,
+                     min(3.0, args.cpu_seconds))
+                if throughput_mode:
+                    ctx.set_solve_mode(R._capi.SOLVE_THROUGHPUT)
+            if world == 1 and args.only is None and not args.no_config2:
+                side("loop_gate_and_search", loop_gate_and_search, R, torch, ctx, submaps, full, mp, weak_prob, not args.no_cpu_baseline, min(2.0, args.cpu_seconds))
+            if args.odometry_scans > 0 and world == 1:
+                side("config3_streaming_odometry", streaming_odometry, ctx, args.odometry_scans, not args.no_cpu_baseline)
+            if args.replica_steps > 0 and world == 1:
+                side("config3_replicas", config3_replicas, ctx, args.replica_steps)
+            if args.cpp_drive_scans > 0 and world == 1:
+                py = out.get("config3_streaming_odometry", {})
+                side("cpp_local_fuser_drive", cpp_local_fuser_drive, ctx, args.cpp_drive_scans, py.get("ms_per_scan") if isinstance(py, dict) else None)
+            if args.polar_scans > 0 and world == 1:
+                side("config5_polar_filter", polar_filter, ctx, args.polar_scans)
+            if args.slam_scans > 0 and world == 1:
+                side("slam_loop", slam_loop, ctx, args.slam_scans)
+            if args.polar_odometry_scans > 0 and world == 1:
+                side("config5_polar_odometry", polar_odometry, ctx, args.polar_odometry_scans)
         print(json.dumps(out))
     if multi:
         dist.barrier()

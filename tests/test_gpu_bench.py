@@ -21,7 +21,7 @@ def _last_json(out):
 
 
 def test_bench_single_gpu_contract():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--odometry-scans", "8", "--polar-scans", "2",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", "1", "--odometry-scans", "8", "--polar-scans", "2",
                         "--cpu-seconds", "0.5", "--min-seconds", "0.1", "--slam-scans", "0", "--polar-odometry-scans", "0",
                         "--replica-steps", "10", "--cpp-drive-scans", "24", "--distinct-inputs", "3"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     d = _last_json(r.stdout)
@@ -73,10 +73,45 @@ def test_bench_single_gpu_contract():
     assert d["pose_err_vs_oracle"]["max_abs_translation_m"] <= 1e-4 and d["pose_err_vs_oracle"]["max_abs_rotation_rad"] <= 1e-4
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_last_step(built, tmp_path):
+    """Without --full: ONE region of exactly --steps timed steps and no side measurement; --dump-outputs holds what the timed
+    path returned in its last step, which for these registrations is what the CPU oracle computes."""
+    import numpy as np
+
+    import pyoracle as po
+    import randt_slam_amd as R
+    from randt_slam_amd import synth
+    from util import oracle_scan_map, oracle_submap, to_oracle_params
+
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(out)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["metric"] == "ndt_registrations_per_sec" and d["unit"] == "registrations/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 7 and d["repeats"] == 1 and len(d["region_ms"]) == 1 and d["value"] > 1e5
+    assert abs(d["ms_per_step"] * d["steps"] * 1e-3 - d["timed_region_s"]) < 1e-9
+    for k in ("sustained", "hbm_achieved", "roofline", "cpu_baseline", "config2_single_pair", "config3_streaming_odometry", "distinct_inputs"):
+        assert k not in d, k
+
+    pose = np.load(out / "pose.npy")
+    assert pose.dtype == np.float64 and pose.shape == (512, 4)
+    fields = [f for f in R.RESULT_DTYPE.names if f != "reserved"]
+    assert sorted(p.name for p in out.iterdir()) == sorted(["pose.npy"] + ["result_%s.npy" % f for f in fields])
+    status = np.load(out / "result_status.npy")
+    assert status.dtype == np.float64 and status.shape == (512,) and (status == 0).all()
+    prob = synth.make_batch_problem(8, 64, 34)                  # bench.py's batch
+    op = to_oracle_params(R.default_matcher_params())
+    g4 = synth.pose3_to_pose4(prob["guess"])
+    for i in (0, 200, 511):
+        rc, p4, _, _ = po.register_pair(oracle_submap(prob["submaps"][prob["submap_of"][i]]), oracle_scan_map(prob["scans"][i]), op, g4[i])
+        assert np.allclose(pose[i], p4, atol=1e-6), (i, pose[i], p4)
+
+
 def test_bench_two_ranks_control_flow():
     env = dict(os.environ, RANDT_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
+           "--master-port", "29533", "bench.py", "--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
            "--odometry-scans", "0", "--polar-scans", "0", "--streams", "2", "--min-seconds", "0.05"]   # two processes share ONE GPU here
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     d = _last_json(r.stdout)
@@ -92,7 +127,7 @@ def test_bench_group_path_on_one_rank():
     the strong region through randt_group_scan_register_batch_dev with the ONE-exchange gather (ncclAllGather of packed rows),
     the same region without the exchange, several groups in flight, and the loud fallback keys -- with a single rank on this
     box's one GPU (--force-group-path): everything except more than one peer."""
-    r = subprocess.run([sys.executable, "bench.py", "--force-group-path", "--steps", "6", "--warmup", "1", "--repeats", "3", "--min-seconds", "0.05",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--force-group-path", "--steps", "6", "--warmup", "1", "--repeats", "3", "--min-seconds", "0.05",
                         "--no-cpu-baseline", "--no-config2", "--no-roofline-sections", "--odometry-scans", "0", "--polar-scans", "0",
                         "--slam-scans", "0", "--polar-odometry-scans", "0", "--streams", "4"], cwd=ROOT, capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, MASTER_PORT="29535"))
@@ -114,7 +149,7 @@ def test_bench_two_ranks_over_rccl_sharing_the_one_gpu():
     from randt_slam_amd import shard
 
     port = 29540
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "2", "--repeats", "3", "--min-seconds", "0.05",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "20", "--warmup", "2", "--repeats", "3", "--min-seconds", "0.05",
            "--no-cpu-baseline", "--no-config2", "--no-roofline-sections", "--odometry-scans", "0", "--polar-scans", "0", "--slam-scans", "0",
            "--polar-odometry-scans", "0", "--streams", "4"]
     procs = [subprocess.Popen(cmd, cwd=ROOT, env=shard.shared_gpu_rank_env(r, 2, port), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
@@ -142,7 +177,7 @@ def test_bench_two_ranks_rccl():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs >= 2 GPUs")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29534", "bench.py", "--gpus", "2", "--steps", "50", "--warmup", "2", "--min-seconds", "0.05"]
+           "--master-port", "29534", "bench.py", "--full", "--gpus", "2", "--steps", "50", "--warmup", "2", "--min-seconds", "0.05"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     d = _last_json(r.stdout)
     assert d["n_gpus"] == 2 and d["strong_scaling"]["poses_bit_identical_to_unsharded"] is True

@@ -1,5 +1,5 @@
 # A/B of the window solve through config 3 (same box, same run): tools/ab_win.sh [variants under build/ab/ ... | base]
-H="--polar-scans 0 --slam-scans 0 --polar-odometry-scans 0 --no-cpu-baseline --no-roofline-sections --steps 200"
+H="--full --polar-scans 0 --slam-scans 0 --polar-odometry-scans 0 --no-cpu-baseline --no-roofline-sections --steps 200"
 for rep in 1 2; do
 for v in "$@"; do
   if [ $v = base ]; then unset RANDT_LIB; else export RANDT_LIB=$PWD/build/ab/$v/librandt_hip.so; fi

@@ -9,6 +9,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
@@ -26,11 +27,12 @@ def regs(tok):
 
 def disassemble(obj):
     """obj: a single-translation-unit host object (window.o): its .hip_fatbin section holds one offload bundle."""
-    fat, tmp = "/tmp/randt_dpp_check.fatbin", "/tmp/randt_dpp_check.co"
-    subprocess.check_call([OBJCOPY, "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
-    subprocess.check_call([BUNDLER, "--type=o", "--unbundle", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + tmp],
-                          stderr=subprocess.DEVNULL)
-    return subprocess.check_output([OBJDUMP, "-d", "--no-show-raw-insn", tmp], text=True)
+    with tempfile.TemporaryDirectory() as d:   # private to this run: another user's leftovers cannot block it
+        fat, tmp = os.path.join(d, "window.fatbin"), os.path.join(d, "window.co")
+        subprocess.check_call([OBJCOPY, "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
+        subprocess.check_call([BUNDLER, "--type=o", "--unbundle", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + tmp],
+                              stderr=subprocess.DEVNULL)
+        return subprocess.check_output([OBJDUMP, "-d", "--no-show-raw-insn", tmp], text=True)
 
 
 def check(text):

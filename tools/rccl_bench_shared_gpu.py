@@ -16,7 +16,7 @@ from randt_slam_amd import shard  # noqa: E402
 
 def main():
     n = int(sys.argv[1])
-    cmd = [sys.executable, "bench.py", "--gpus", str(n), "--steps", "40", "--warmup", "4", "--repeats", "3", "--min-seconds", "0.05", "--streams", "4",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", str(n), "--steps", "40", "--warmup", "4", "--repeats", "3", "--min-seconds", "0.05", "--streams", "4",
            "--no-cpu-baseline", "--no-config2", "--no-roofline-sections", "--odometry-scans", "0", "--polar-scans", "0", "--slam-scans", "0",
            "--polar-odometry-scans", "0", "--cpp-drive-scans", "0", "--replica-steps", "0", "--distinct-inputs", "0", "--no-auto-region"]
     port = 29600 + n

@@ -4,7 +4,7 @@ python - <<'P'
 import os, subprocess, sys, json
 sys.path.insert(0, os.getcwd())
 from randt_slam_amd import shard
-cmd=[sys.executable,"bench.py","--gpus","2","--steps","200","--warmup","5","--no-cpu-baseline","--no-config2","--no-roofline-sections","--odometry-scans","0","--polar-scans","0","--slam-scans","0","--polar-odometry-scans","0","--cpp-drive-scans","0","--replica-steps","0","--distinct-inputs","0","--no-auto-region"]
+cmd=[sys.executable,"bench.py","--full","--gpus","2","--steps","200","--warmup","5","--no-cpu-baseline","--no-config2","--no-roofline-sections","--odometry-scans","0","--polar-scans","0","--slam-scans","0","--polar-odometry-scans","0","--cpp-drive-scans","0","--replica-steps","0","--distinct-inputs","0","--no-auto-region"]
 ps=[subprocess.Popen(cmd, env=shard.shared_gpu_rank_env(r,2,29577), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(2)]
 outs=[p.communicate(timeout=600) for p in ps]
 open("gpurun_out/rccl/bench_gpus2_shared_gpu.json","w").write(outs[0][0])
