@@ -5,8 +5,8 @@
 // (src/ndt_representation/ndt_map.cpp:101-175) and Cell::mahalanobisSquaredIntensity
 // (src/ndt_representation/ndt_cell.cpp:172-176).
 //
-// One workgroup (256 threads) per (scan, submap) pair -- per FOUR pairs, one after the other, when batches share the chip; per
-// (pair, chunk) for a lone batch (launch_associate below) --, phases per chunk of 64 moving cells so that every
+// One workgroup (256 threads) per (scan, submap) pair -- per (pair, chunk) for a lone batch (launch_associate below) --, phases
+// per chunk of 64 moving cells so that every
 // global-memory round trip is taken once by all lanes together instead of once per cell, and so that the per-cell
 // logic runs one THREAD per cell (64 cells per wave-instruction) instead of one wavefront per cell:
 //   P0  a ring-major table of the (2R+1)^2 window offsets is built; optionally (RANDT_ASSOC_STAGE_GRID=1) the
@@ -130,9 +130,10 @@ __global__ __launch_bounds__(ASSOC_BLOCK) __attribute__((amdgpu_waves_per_eu(TP 
   // k_ndt_build (profiles/experiments/r03_issue_priority.md).
   __builtin_amdgcn_s_setprio(RANDT_LATENCY_KERNEL_PRIO);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // TP: a workgroup walks `ppw` pairs one after the other -- in the pipelined region fewer, longer-lived workgroups are cheaper than
-  // many short ones (4 per workgroup: +2 %; spreading a pair's chunks over workgroups, the lone-batch placement: -3 .. -7 %).  A
-  // compile-time single trip otherwise, so the lone-batch instantiations keep their code.
+  // TP: a workgroup walks `ppw` pairs one after the other (RANDT_ASSOC_TP_PPW; default one: with four a 512-pair launch was 128
+  // workgroups and took 82 us under load against 28 us at one pair each, profiles/experiments/r07_assoc_one_pair_per_workgroup.md;
+  // spreading a pair's chunks over workgroups, the lone-batch placement, is slower in both regions).  A compile-time single trip
+  // otherwise, so the lone-batch instantiations keep their code.
   const int n_walk = TP ? ppw : 1;
   for (int pp = 0; pp < n_walk; ++pp) {
   const int pair = TP ? (int)blockIdx.x * ppw + pp : (int)blockIdx.x;
@@ -559,8 +560,8 @@ int launch_associate_cfg(randt_ctx* ctx, const MapView& fixed, const int32_t* d_
     if (split < 1) split = 1;
   }
   RANDT_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_associate<STAGE, CH, TP, WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  // pairs per workgroup: the walk is for callers that keep several batches in flight (or a batch that fills the chip several
-  // times over); a lone batch of a few hundred pairs more than the split geometry takes stays one pair per workgroup
+  // pairs per workgroup (ctx->assoc_tp_ppw, 1 by default): taken by callers that keep several batches in flight (or a batch that
+  // fills the chip several times over); a lone batch of a few hundred pairs more than the split geometry takes stays at one
   const bool walk = TP && (n_pairs >= 8 * ctx->n_cus || shared);
   const int ppw = walk ? (ctx->assoc_tp_ppw > 0 ? ctx->assoc_tp_ppw : 1) : 1;
   hipLaunchKernelGGL((k_associate<STAGE, CH, TP, WIDE>), dim3((n_pairs + ppw - 1) / ppw, split), dim3(ASSOC_BLOCK), lds, ctx->stream, fixed, d_fixed_idx, moving,

@@ -69,7 +69,10 @@ struct randt_ctx {
   int window_general = 0;            // RANDT_WINDOW_GENERAL=1: every window takes window_gen.hip (tests: the two kernels agree)
   int debug_force_misrank = 0;       // RANDT_DEBUG_FORCE_MISRANK=1: test hook, makes the in-kernel order check fail
   int build_tiled = 0;       // RANDT_BUILD_TILED=1: every scan through the multi-workgroup build (normally only > 7168 points)
-  int assoc_tp_ppw = 4;      // pairs per association workgroup when batches share the chip (RANDT_ASSOC_TP_PPW)
+  int assoc_tp_ppw = 1;      // pairs per association workgroup when batches share the chip (RANDT_ASSOC_TP_PPW).  Round 3 walked four
+                             // pairs per workgroup (+2 % steady on 16 hardware queues); on 4 queues every stream's launches run in a
+                             // chain and the walk's 82 us association sat in it: one pair per workgroup takes 28 us, K = 20 burst
+                             // 1.72 -> 1.56 ms, steady step 74 -> 67 us (profiles/experiments/r07_assoc_one_pair_per_workgroup.md)
   int assoc_tp_ch = 64;      // cells per chunk of the association when batches share the chip (16 / 32 / 48 / 64; RANDT_ASSOC_TP_CH)
   int assoc_stage_grid = 0;  // 1: stage the fixed map's index grid in LDS; 0: gather it from L2 (same speed alone, but 36 KB instead of 76 KB of LDS leaves room for co-running build workgroups: +2 % end to end)
   // ---- device storage pool (api.hip, randt_dev_alloc / randt_dev_release): the blocks of destroyed map batches and of the
