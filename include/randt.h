@@ -572,6 +572,18 @@ void randt_pg_params_default(randt_pg_params* p);
 int randt_pose_graph_optimize(randt_ctx* ctx, int n_poses, double* h_poses, int n_edges, const int32_t* h_id_begin,
                               const int32_t* h_id_end, const double* h_meas, const double* h_sqrt_info,
                               int max_update_index, const randt_pg_params* p, randt_pg_result* out);
+/* Marginal covariances of the pose graph (the ceres::Covariance block of global_fuser.cpp:62-87, commented out in the
+ * reference): with J the stacked edge Jacobians at h_poses (sqrt-information applied, and the sqrt(rho') scaling of the
+ * Huber loss when p->use_robust_loss is set), over the edges that pass the max_update_index rule, and pose `anchor_pose`
+ * held constant (-1 = the last pose, the reference's choice), h_cov[i] is the 3x3 block (H^-1)_ii of H = J^T J, row-major
+ * (x, y, yaw), without any damping.  The anchor and poses that no used edge touches get zeros.  Only use_robust_loss and
+ * loss_scale of p are read.  The factorisation is the optimiser's (chain segments + dense Schur complement); on top of
+ * it the selected inverse, with one more (3 n_sep)^2 buffer.  RANDT_ERR_INVALID for an anchor or an edge out of range
+ * and for a graph whose variable poses are not all connected to the anchor (randt_last_error says "rank deficient");
+ * h_cov is written only on success.  RANDT_ERR_UNSUPPORTED beyond RANDT_PG_MAX_SEPARATORS. */
+int randt_pose_graph_covariance(randt_ctx* ctx, int n_poses, const double* h_poses, int n_edges, const int32_t* h_id_begin,
+                                const int32_t* h_id_end, const double* h_meas, const double* h_sqrt_info,
+                                int max_update_index, const randt_pg_params* p, int anchor_pose, double* h_cov);
 
 /* ------------------------------------------------------------------ multi-GPU group (8e) ----- */
 /* Independent scan-to-submap registrations -- the loop-closure candidates LocalFuser::detectLoopClosures hands to

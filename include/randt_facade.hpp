@@ -1172,6 +1172,9 @@ struct Constraint {
 struct GlobalFuserParameters {  // include/ndt_slam/ndt_slam_parameters.h:134-139
   double loss_function_scale = 60.0;
   bool use_robust_loss = false;
+  // NOT a reference parameter: run the ceres::Covariance block of global_fuser.cpp:62-87 (commented out there) after a
+  // successful optimisation and fill Pose::cov_pos_pos / cov_pos_rot / cov_rot_rot (randt_pose_graph_covariance)
+  bool compute_covariance = false;
 };
 
 // GlobalFuser (include/global_fuser/global_fuser.h:32-60, src/global_fuser/global_fuser.cpp:7-105)
@@ -1188,7 +1191,8 @@ class GlobalFuser {
   //                        int max_update_index)                                        (global_fuser.cpp:13-105)
   // Same protocol: copy the nodes under the mutex, optimise the copy, write back keys 0..size-1 under the mutex.  Node
   // keys must be 0..size-1 (the reference's write-back loop assumes it, :100-102).  On a solver error the nodes are left
-  // as they were and a warning goes to std::cout.
+  // as they were and a warning goes to std::cout.  With GlobalFuserParameters::compute_covariance the covariance members
+  // of every node are filled as well; if that call fails the poses are still written back and the covariances stay as they were.
   void optimizePoseGraph(std::map<int, Pose>& poses_ref, const std::vector<Constraint>& edges, std::mutex& poses_mutex,
                          int max_update_index) {
     std::unique_lock<std::mutex> lock(poses_mutex);
@@ -1226,6 +1230,24 @@ class GlobalFuser {
     }
     std::cout << "Ceres-style report: iterations " << res.iterations << ", initial cost " << res.initial_cost << ", final cost "
               << res.final_cost << ", termination " << res.termination << '\n';
+    if (parameters_.compute_covariance) {
+      // global_fuser.cpp:62-87: the first pose variable again, the LAST one constant (:68-69), the pos/pos, pos/rot and
+      // rot/rot blocks of every node (:74-83) -- at the optimised poses, with the loss applied (Covariance::Options' default)
+      std::vector<double> cov(9 * static_cast<size_t>(n));
+      const int crc = randt_pose_graph_covariance(ctx_->get(), n, x.data(), static_cast<int>(edges.size()), ia.data(), ib.data(), meas.data(),
+                                                  sqi.data(), max_update_index, &pp, -1, cov.data());
+      if (crc != RANDT_OK) {
+        std::cout << "WARNING: pose graph covariance failed: " << randt_last_error(ctx_->get()) << std::endl;
+      } else {
+        for (int i = 0; i < n; ++i) {
+          Pose& p = poses.at(i);
+          const double* c = &cov[9 * static_cast<size_t>(i)];
+          p.cov_pos_pos = {c[0], c[1], c[3], c[4]};
+          p.cov_pos_rot = {c[2], c[5]};
+          p.cov_rot_rot = c[8];
+        }
+      }
+    }
     for (int i = 0; i < n; ++i) {
       Pose& p = poses.at(i);
       p.pos = {x[3 * i + 0], x[3 * i + 1]};

@@ -3,7 +3,7 @@
 // rc::navigation::ndt::LocalFuser (include/local_fuser/local_fuser.h:46-141) orchestrates scan -> NDT -> predict -> fixed-lag
 // registration -> keyframe queue -> rolling submap -> graph node, submap roll-over with overlap, loop-closure candidates and the
 // current submap's origin after a pose-graph optimisation.  This header holds its DATA PATH -- processScan (local_fuser.cpp:99-300),
-// initializeNewSubmap (:40-63), detectLoopClosures (:318-350, Scan Context branch), getTransform, submapComplete, and
+// initializeNewSubmap (:40-63), detectLoopClosures (:318-416: the Scan Context branch and, opt-in, the covariance-gated one), getTransform, submapComplete, and
 // NDTSlam::optimizePoseGraph's call into GlobalFuser (ndt_slam.cpp:351-361) with the pose part of updateSubmaps (local_fuser.cpp:65-88)
 // -- written against the facade classes exactly as the reference writes it against its own Matcher / Map / HierarchicalMap /
 // SCManager / GlobalFuser: Maps by value in the same places, the reference-signature Matcher::estimateTransformCeres.  Not here: ROS
@@ -55,6 +55,11 @@ struct LocalFuserParameters {
   GlobalFuserParameters global_fuser_parameters;
   int submap_size_poses = 135, submap_overlap = 20, insertion_step = 4;
   bool use_scan_context_as_loop_closure = false;      // the graph / loop-closure layer on top of the odometry
+  // the loop search WITHOUT Scan Context (local_fuser.cpp:351-412, dead in the reference because its covariance block is commented
+  // out): candidates by Mahalanobis distance under the nodes' marginal covariances (GlobalFuserParameters::compute_covariance)
+  bool use_covariance_gated_loop_closure = false;
+  bool compute_dfs_loop_closure = false;                // base yaml :25: estimateTransformGlobalBNB before the refinement
+  double max_data_association_mahalanobis_dist = 0.5;  // base yaml :26
   int loop_closure_gnc_steps = 2;
   bool use_intensity_in_loop_closure = true;          // ndt_slam.cpp:614-616: defaults to ndt_matcher.use_intensity_as_dimension
   double loop_closure_scale = 1.5, loop_closure_max_cs_divergence = 3.6, loop_closure_weight = 4.0e4;
@@ -88,6 +93,12 @@ class LocalFuser {
       slam_ = true;
       sc_manager_.initialize(ctx_, parameters.scan_context_parameters);
       global_fuser_.initialize(ctx_, parameters.global_fuser_parameters);
+    } else if (parameters.use_covariance_gated_loop_closure) {
+      slam_ = true;
+      covariance_gated_ = true;   // no Scan Context database; the covariances come from the back end
+      GlobalFuserParameters gp = parameters.global_fuser_parameters;
+      gp.compute_covariance = true;
+      global_fuser_.initialize(ctx_, gp);
     }
   }
 
@@ -99,8 +110,70 @@ class LocalFuser {
   const std::vector<LoopLog>& loopLog() const { return loop_log_; }
   const std::vector<Constraint>& edges() const { return edges_; }
 
-  // LocalFuser::detectLoopClosures, Scan Context branch (local_fuser.cpp:318-350)
+  // LocalFuser::detectLoopClosures, the branch without Scan Context (local_fuser.cpp:351-412), quirks included: per finished submap
+  // the node closest to the query in Mahalanobis distance under the NODE's cov_pos_pos (:357, "mathematically incorrect for
+  // manifold" there), optionally estimateTransformGlobalBNB with a window sized from the node's covariance (:380-387), then the
+  // refinement and the CS gate of the other branch.  A node whose cov_pos_pos is not positive definite (never covered by an
+  // optimisation: zeros) is skipped -- there the inverse of a zero matrix gives NaN and `NaN < thr` is false.
+  int detectLoopClosuresCovarianceGated() {
+    int added = 0;
+    const double thr = parameters_.max_data_association_mahalanobis_dist;
+    while (!_next_maps_to_search_loop.empty()) {
+      const int q = _next_maps_to_search_loop.front();
+      _next_maps_to_search_loop.pop_front();
+      std::map<int, std::pair<int, double>> best_submap_matches;
+      const Pose& pq = nodes_.at(q);
+      for (const auto& pose_i : nodes_) {
+        const int sub_i = submap_idzs_.at(pose_i.first);
+        if (sub_i == submap_idzs_.at(q) || sub_i == n_finished_submaps_ || !submaps_.count(sub_i)) continue;   // :355
+        const std::array<double, 4>& P = pose_i.second.cov_pos_pos;
+        const double a = P[0], b = P[1], c = P[2], d = P[3], det = a * d - b * c;
+        if (!(a > 0.0 && det > 0.0)) continue;
+        const double dx = pq.pose.d[2] - pose_i.second.pose.d[2], dy = pq.pose.d[3] - pose_i.second.pose.d[3];
+        const double dist = std::sqrt((d * dx * dx - (b + c) * dx * dy + a * dy * dy) / det);                 // :357
+        if (dist < thr) {                                                                                     // :358-362
+          auto it = best_submap_matches.find(sub_i);
+          if (it == best_submap_matches.end() || dist < it->second.second) best_submap_matches[sub_i] = std::make_pair(pose_i.first, dist);
+        }
+      }
+      for (const auto& match : best_submap_matches) {
+        const int sub_i = match.first, lid = match.second.first;
+        Map f_loop_map = submaps_.at(sub_i);   // :370
+        Map m_loop_map = scans_.at(q);         // :371
+        SE2d trans = se2_mul(se2_inv(nodes_.at(root_nodes_.at(sub_i)).pose), pq.pose);   // :376
+        if (parameters_.compute_dfs_loop_closure) {                                       // :379-388
+          const std::array<double, 9>& cov = nodes_.at(lid).cov;
+          const double ca = cov[0], cc = cov[3], cd = cov[4];   // self-adjoint xy block, lower triangle read like Eigen does
+          const double lam0 = 0.5 * (ca + cd) - std::sqrt(0.25 * (ca - cd) * (ca - cd) + cc * cc);   // eigenvalues()(0): the SMALLER one
+          const double search_window_linear = thr * std::abs(lam0);   // named "max" there, and no root is taken: kept
+          const double search_window_angular = std::min(2 * M_PI, thr * std::sqrt(cov[8]));
+          ndt_matcher_.estimateTransformGlobalBNB(trans, f_loop_map, m_loop_map, parameters_.use_intensity_in_loop_closure,
+                                                  parameters_.loop_closure_scale, search_window_linear, search_window_angular);
+        }
+        ndt_matcher_.estimateLoopConstraint(trans, f_loop_map, m_loop_map, parameters_.loop_closure_gnc_steps, parameters_.use_intensity_in_loop_closure,
+                                            parameters_.loop_closure_scale);   // :395
+        m_loop_map.transformMap(trans);                                        // :396
+        const double cs = f_loop_map.calculateCSDivergence(m_loop_map);        // :397
+        const bool ok = cs < parameters_.loop_closure_max_cs_divergence;       // :402
+        loop_log_.push_back({q, lid, cs, ok});
+        if (ok) {                                                              // :403-409
+          Constraint c;
+          c.id_begin = root_nodes_.at(sub_i);
+          c.id_end = q;
+          c.trans = trans;
+          const double w = parameters_.loop_closure_weight;
+          c.sqrt_information = {w, 0, 0, 0, w, 0, 0, 0, w};
+          edges_.push_back(c);
+          ++added;
+        }
+      }
+    }
+    return added;
+  }
+
+  // LocalFuser::detectLoopClosures (local_fuser.cpp:318-416): the Scan Context branch (:322-350) below, the other one above
   int detectLoopClosures() {
+    if (covariance_gated_) return detectLoopClosuresCovarianceGated();
     int added = 0;
     while (!_next_maps_to_search_loop.empty()) {
       const int q = _next_maps_to_search_loop.front();
@@ -384,14 +457,15 @@ class LocalFuser {
     nodes_[nid] = p;
     submap_idzs_.push_back(n_finished_submaps_);
     scans_[nid] = scan;                                  // kept alive for loop registration (a value: shares the storage)
-    sc_manager_.makeAndSaveScancontextAndKeys(points.data(), static_cast<int>(points.size()) / cur_stride_, cur_stride_, cur_ioff_, {pose.d[2], pose.d[3]},
-                                              p.traversed_dist);   // :207, :281
+    if (!covariance_gated_)
+      sc_manager_.makeAndSaveScancontextAndKeys(points.data(), static_cast<int>(points.size()) / cur_stride_, cur_stride_, cur_ioff_, {pose.d[2], pose.d[3]},
+                                                p.traversed_dist);   // :207, :281
     return nid;
   }
 
   std::shared_ptr<Context> ctx_;
   LocalFuserParameters parameters_;
-  bool slam_ = false;
+  bool slam_ = false, covariance_gated_ = false;
   SCManager sc_manager_;
   GlobalFuser global_fuser_;
   std::mutex nodes_mutex_;

@@ -166,6 +166,7 @@ SYMBOLS = {
     "randt_sc_db_download": (_I, [_V, _I, _V, _V, _V]),
     "randt_pg_params_default": (None, [_P(PgParams)]),
     "randt_pose_graph_optimize": (_I, [_V, _I, _V, _I, _V, _V, _V, _V, _I, _P(PgParams), _P(PgResult)]),
+    "randt_pose_graph_covariance": (_I, [_V, _I, _V, _I, _V, _V, _V, _V, _I, _P(PgParams), _I, _V]),
     "randt_predict_state": (_I, [_V, C.c_double, _V]),
     "randt_predict_state_param": (_I, [_V, C.c_double, _I, _V]),
     "randt_predict_state_batch": (_I, [_V, _I, C.c_double, _I, _V]),

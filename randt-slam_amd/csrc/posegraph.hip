@@ -20,6 +20,8 @@
 // That is block Cholesky in a nested-dissection order -- no Woodbury-style cancellation when loop closures carry
 // weights of 4e4 (parameters_indoor.yaml:10).  Everything is fp64 and deterministic (gathers through host-built
 // incidence lists and fixed-order reductions; no floating-point atomics).
+// The same factor, undamped, also gives the marginal covariance of every pose (randt_pose_graph_covariance: the
+// ceres::Covariance block of global_fuser.cpp:62-87, commented out in the reference) -- the k_pg_cov_* kernels below.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -60,6 +62,7 @@ struct PgDev {
   double *p_gabs, *p_xsq, *p_sn, *p_mcc;  // per-pose / per-edge partials
   double *scal;                            // [8]: cost cur, cost cand, mcc sum, step norm^2, x norm^2, grad max
   int32_t* flags;                          // [0] factor ok, [1] dense ok, [2] step finite
+  double *Mt, *cov;  // covariance path only: [ns][ns] transposed inverse of the dense factor, [n_poses][9] output
 };
 
 __device__ __forceinline__ double pg_normalize_angle(double a) {
@@ -672,60 +675,262 @@ struct Carver {  // bump allocator over one device block
 
 inline int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
 
-}  // namespace
+// ---- marginal covariances: selected inverse of H = J^T J (no damping) on top of the factor above.  Everything runs in
+// the optimiser's Jacobi-scaled coordinates (H_s = D H D, D = diag(sigma)) and k_pg_cov_gather undoes the scaling at the
+// very end: Sigma = D Sigma_s D.
+//   separators: Sigma_ss = (S - C^T W)^-1 = M^T M with M = L^-1, L the dense factor in Sw.  k_pg_cov_trinv writes M
+//               transposed (Mt[c][r] = M[r][c], r >= c), so that the entries of Sigma_ss that are consumed -- the diagonal
+//               3x3 blocks and the block between the two separators that bound one segment -- are dot products of
+//               contiguous rows (k_pg_cov_sep_blocks); they land in S0, which nothing reads after k_pg_schur.
+//   interiors:  Sigma_mm = (T^-1)_mm + W_m Sigma_ss[{l,r},{l,r}] W_m^T; (T^-1)_mm by the backward recurrence over the
+//               block-bidiagonal factor (k_pg_cov_chain, into E, which nothing reads after k_pg_factor).
 
-void randt_pg_params_default(randt_pg_params* p) {
-  if (!p) return;
-  memset(p, 0, sizeof(*p));
-  p->use_robust_loss = 0;
-  p->loss_scale = 60.0;
-  p->max_iterations = 200000;  // global_fuser.cpp:52
-  p->max_consecutive_invalid_steps = 5;
-  p->function_tolerance = 1e-6;
-  p->gradient_tolerance = 1e-10;
-  p->parameter_tolerance = 1e-8;
-  p->initial_radius = 1e4;
-  p->max_radius = 1e16;
-  p->min_radius = 1e-32;
-  p->min_relative_decrease = 1e-3;
-  p->min_lm_diagonal = 1e-6;
-  p->max_lm_diagonal = 1e32;
+// M = L^-1 column by column: a column of M depends on L and on itself only, so one workgroup owns 8 columns
+// (block column bj of PG_NB, strip of 8) and walks down the block rows: M[i, j] = Linv_i (I[i, j] - sum_{j <= k < i} L[i, k] M[k, j]).
+// thread = (row r of the block, column c of the strip)
+__global__ __launch_bounds__(256) void k_pg_cov_trinv(PgDev d) {
+  __shared__ double lt[PG_NB][PG_NB + 1];
+  __shared__ double li[PG_NB][PG_NB + 1];
+  __shared__ double ms[8][PG_NB + 1];
+  __shared__ double y[PG_NB][9];
+  const int n = d.ns, nblk = (n + PG_NB - 1) / PG_NB, tid = threadIdx.x;
+  const int bj = blockIdx.x, c0 = bj * PG_NB + 8 * (int)blockIdx.y;
+  if (c0 >= n) return;
+  const int r = tid % PG_NB, c = tid / PG_NB;
+  const double* L = d.Sw;
+  double* Mt = d.Mt;
+  for (int i = bj; i < nblk; ++i) {
+    double acc = (i == bj && r == 8 * (int)blockIdx.y + c) ? 1.0 : 0.0;
+    for (int k = bj; k < i; ++k) {
+      for (int t = tid; t < PG_NB * PG_NB; t += 256) {
+        const int rr = t / PG_NB, p = t % PG_NB;
+        lt[rr][p] = (i * PG_NB + rr < n) ? L[(size_t)(i * PG_NB + rr) * n + k * PG_NB + p] : 0.0;
+      }
+      {  // Mt row c0 + c is written from column c0 + c on
+        const int col = c0 + c, kk = k * PG_NB + r;
+        ms[c][r] = (col < n && kk >= col) ? Mt[(size_t)col * n + kk] : 0.0;
+      }
+      __syncthreads();
+#pragma unroll 8
+      for (int p = 0; p < PG_NB; ++p) acc -= lt[r][p] * ms[c][p];
+      __syncthreads();
+    }
+    y[r][c] = acc;
+    for (int t = tid; t < PG_NB * PG_NB; t += 256) li[t / PG_NB][t % PG_NB] = d.Linv[(size_t)i * PG_NB * PG_NB + t];
+    __syncthreads();
+    double out = 0.0;
+    for (int p = 0; p <= r; ++p) out += li[r][p] * y[p][c];
+    if (i * PG_NB + r < n && c0 + c < n) Mt[(size_t)(c0 + c) * n + i * PG_NB + r] = out;
+    __syncthreads();  // the rows just written are read back as ms in the next block rows
+  }
 }
 
-int randt_pose_graph_optimize(randt_ctx* ctx, int n_poses, double* h_poses, int n_edges, const int32_t* h_id_begin,
-                                         const int32_t* h_id_end, const double* h_meas, const double* h_sqrt_info,
-                                         int max_update_index, const randt_pg_params* opt, randt_pg_result* out) {
-  DeviceGuard dev_guard__(ctx);
-  if (!ctx || !opt || n_poses <= 0 || n_edges < 0 || !h_poses) return RANDT_ERR_INVALID;
-  if (n_edges > 0 && (!h_id_begin || !h_id_end || !h_meas || !h_sqrt_info)) return RANDT_ERR_INVALID;
-  if (out) {
-    memset(out, 0, sizeof(*out));
-    out->n_loop_closures = n_edges + 1 - n_poses;  // global_fuser.cpp:26
+// The consumed 3x3 blocks of Sigma_ss = M^T M: workgroup b < n_sep the diagonal block of separator b, workgroup
+// n_sep + s the block (l, r) of the separators bounding segment s.  Entry (a, b) = sum_{k >= max(a, b)} Mt[a][k] Mt[b][k];
+// per-thread partial sums in index order, then a fixed tree: deterministic.
+__global__ __launch_bounds__(256) void k_pg_cov_sep_blocks(PgDev d) {
+  __shared__ double sh[9][256];
+  const int n = d.ns, tid = threadIdx.x;
+  int qa, qb;
+  if ((int)blockIdx.x < d.n_sep) {
+    qa = qb = blockIdx.x;
+  } else {
+    const int m0 = d.seg_first[blockIdx.x - d.n_sep];
+    qa = d.bndL[m0];
+    qb = d.bndR[m0];
+    if (qa < 0 || qb < 0) return;
   }
-  // ---- the residual blocks the reference adds (global_fuser.cpp:31-46)
-  std::vector<int32_t> ia, ib;
+  const double* Mt = d.Mt;
+  double acc[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) acc[i] = 0.0;
+  for (int k = 3 * max(qa, qb) + tid; k < n; k += 256) {
+    double va[3], vb[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      va[i] = k >= 3 * qa + i ? Mt[(size_t)(3 * qa + i) * n + k] : 0.0;
+      vb[i] = k >= 3 * qb + i ? Mt[(size_t)(3 * qb + i) * n + k] : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) acc[i * 3 + j] += va[i] * vb[j];
+  }
+#pragma unroll
+  for (int i = 0; i < 9; ++i) sh[i][tid] = acc[i];
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off)
+#pragma unroll
+      for (int i = 0; i < 9; ++i) sh[i][tid] += sh[i][tid + off];
+    __syncthreads();
+  }
+  if (tid < 9) d.S0[(size_t)(3 * qa + tid / 3) * n + 3 * qb + tid % 3] = sh[tid][0];
+}
+
+// Diagonal blocks of T^-1 per chain segment, one lane per segment, from the last interior backwards:
+// Z_last = (L L^T)^-1, Z_m = L_mm^-T (I + F_m^T Z_{m+1} F_m) L_mm^-1 with F_m = L[m+1, m].  Written to E (symmetric, row-major).
+__global__ __launch_bounds__(64) void k_pg_cov_chain(PgDev d) {
+  const int sgi = blockIdx.x * 64 + threadIdx.x;
+  if (sgi >= d.n_seg) return;
+  const int m0 = d.seg_first[sgi], n = d.seg_len[sgi];
+  double Z[9];
+  for (int t = n - 1; t >= 0; --t) {
+    const int m = m0 + t;
+    const double* Lf = d.Lf + 9 * (size_t)m;
+    const double l10 = Lf[1], l20 = Lf[3], l21 = Lf[4], i00 = Lf[6], i11 = Lf[7], i22 = Lf[8];
+    double A[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    if (t + 1 < n) {
+      const double* F = d.Ff + 9 * (size_t)m;
+      double G[9];  // Z_{m+1} F
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) G[i * 3 + j] = Z[i * 3 + 0] * F[0 + j] + Z[i * 3 + 1] * F[3 + j] + Z[i * 3 + 2] * F[6 + j];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+          const double v = F[0 + i] * G[0 + j] + F[3 + i] * G[3 + j] + F[6 + i] * G[6 + j];
+          A[i * 3 + j] += v;
+          if (j > i) A[j * 3 + i] += v;
+        }
+    }
+    double B[9];  // B L = A, row by row
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const double b2 = A[i * 3 + 2] * i22;
+      const double b1 = (A[i * 3 + 1] - b2 * l21) * i11;
+      const double b0 = (A[i * 3 + 0] - b1 * l10 - b2 * l20) * i00;
+      B[i * 3 + 0] = b0; B[i * 3 + 1] = b1; B[i * 3 + 2] = b2;
+    }
+    double Y[9];  // L^T Y = B, column by column
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double z2 = B[6 + j] * i22;
+      const double z1 = (B[3 + j] - l21 * z2) * i11;
+      const double z0 = (B[0 + j] - l10 * z1 - l20 * z2) * i00;
+      Y[0 + j] = z0; Y[3 + j] = z1; Y[6 + j] = z2;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) Z[i * 3 + j] = 0.5 * (Y[i * 3 + j] + Y[j * 3 + i]);
+    double* o = d.E + 9 * (size_t)m;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) o[i] = Z[i];
+  }
+}
+
+// One thread per pose: assemble the 3x3 marginal, undo the Jacobi scaling, write cov[v] row-major (x, y, yaw).
+// Constant and untouched poses get zeros.
+__global__ __launch_bounds__(256) void k_pg_cov_gather(PgDev d) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= d.n_poses) return;
+  double* o = d.cov + 9 * (size_t)v;
+  if (!d.is_var[v]) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) o[i] = 0.0;
+    return;
+  }
+  const int n = d.ns, m = d.int_of[v], q = d.sep_of[v];
+  double S[9];
+  if (q >= 0) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) S[i * 3 + j] = d.S0[(size_t)(3 * q + i) * n + 3 * q + j];
+  } else {
+    const int bl = d.bndL[m], br = d.bndR[m];
+    double P[6][6];  // Sigma_ss on (l, r); a missing bound contributes nothing (its W columns are zero as well)
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) P[i][j] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        if (bl >= 0) P[i][j] = d.S0[(size_t)(3 * bl + i) * n + 3 * bl + j];
+        if (br >= 0) P[3 + i][3 + j] = d.S0[(size_t)(3 * br + i) * n + 3 * br + j];
+        if (bl >= 0 && br >= 0) P[i][3 + j] = P[3 + j][i] = d.S0[(size_t)(3 * bl + i) * n + 3 * br + j];
+      }
+    double w[3][6], T[3][6];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) w[i][j] = d.W[(size_t)(3 * m + i) * 8 + j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) a += w[i][k] * P[k][j];
+        T[i][j] = a;
+      }
+    const double* Z = d.E + 9 * (size_t)m;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = i; j < 3; ++j) {
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          a += T[i][k] * w[j][k];
+          b += T[j][k] * w[i][k];
+        }
+        S[i * 3 + j] = S[j * 3 + i] = Z[i * 3 + j] + 0.5 * (a + b);
+      }
+  }
+  const double* sg = d.sigma + 3 * (size_t)v;
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double val = S[i * 3 + j] * (sg[i] * sg[j]);
+      finite = finite && isfinite(val);
+      o[i * 3 + j] = val;
+    }
+  if (!finite) d.flags[2] = 0;
+}
+
+// ---- set-up shared by randt_pose_graph_optimize and randt_pose_graph_covariance: the residual blocks the reference adds,
+// the elimination order and the incidence lists on the host, then one device block carved for everything, and the uploads.
+struct PgHost {
+  std::vector<int32_t> ia, ib, is_var, int_of, sep_of, int_pose, sep_pose, seg_first, seg_len, bndL, bndR, nbL, nbR, inc_off, inc_ent;
   std::vector<double> meas, sqi;
-  std::vector<int32_t> is_var(n_poses, 0);
+  int nu = 0, n_var = 0, n_int = 0, n_sep = 0, ns = 0, n_seg = 0;
+};
+
+// The residual blocks the reference adds (global_fuser.cpp:31-46); pose `fixed` is held constant.
+int pg_filter_edges(randt_ctx* ctx, int n_poses, int n_edges, const int32_t* h_id_begin, const int32_t* h_id_end, const double* h_meas,
+                    const double* h_sqrt_info, int max_update_index, int fixed, PgHost& h) {
+  h.is_var.assign(n_poses, 0);
   for (int e = 0; e < n_edges; ++e) {
     const int a = h_id_begin[e], b = h_id_end[e];
     if (!(a + 1 == b || b <= max_update_index)) continue;
     if (a < 0 || b < 0 || a >= n_poses || b >= n_poses || a == b)
       return randt_set_error(ctx, RANDT_ERR_INVALID, "pose graph: edge endpoints out of range or identical", hipSuccess);
-    ia.push_back(a);
-    ib.push_back(b);
-    meas.insert(meas.end(), h_meas + 3 * (size_t)e, h_meas + 3 * (size_t)e + 3);
-    sqi.insert(sqi.end(), h_sqrt_info + 9 * (size_t)e, h_sqrt_info + 9 * (size_t)e + 9);
-    is_var[a] = is_var[b] = 1;
+    h.ia.push_back(a);
+    h.ib.push_back(b);
+    h.meas.insert(h.meas.end(), h_meas + 3 * (size_t)e, h_meas + 3 * (size_t)e + 3);
+    h.sqi.insert(h.sqi.end(), h_sqrt_info + 9 * (size_t)e, h_sqrt_info + 9 * (size_t)e + 9);
+    h.is_var[a] = h.is_var[b] = 1;
   }
-  is_var[0] = 0;  // poses.begin(): SetParameterBlockConstant (:48-49)
-  const int nu = (int)ia.size();
-  int n_var = 0;
-  for (int i = 0; i < n_poses; ++i) n_var += is_var[i];
-  if (out) out->n_residual_blocks = nu;
-  if (nu == 0 || n_var == 0) return RANDT_OK;
+  h.is_var[fixed] = 0;  // poses.begin(): SetParameterBlockConstant (:48-49); the covariance path fixes its anchor instead
+  h.nu = (int)h.ia.size();
+  h.n_var = 0;
+  for (int i = 0; i < n_poses; ++i) h.n_var += h.is_var[i];
+  return RANDT_OK;
+}
 
-  // ---- elimination order: separators last.  Besides the poses loop closures touch, every seg_cap-th pose of a long
-  // uninterrupted run becomes a separator too: the chain recurrences are serial, so shorter segments = more lanes busy.
+// Elimination order: separators last.  Besides the poses loop closures touch, every seg_cap-th pose of a long
+// uninterrupted run becomes a separator too: the chain recurrences are serial, so shorter segments = more lanes busy.
+void pg_order(int n_poses, PgHost& h) {
+  const int nu = h.nu;
+  const std::vector<int32_t>&ia = h.ia, &ib = h.ib, &is_var = h.is_var;
   std::vector<int32_t> is_sep(n_poses, 0);
   for (int e = 0; e < nu; ++e) {
     const int a = ia[e], b = ib[e];
@@ -740,57 +945,74 @@ int randt_pose_graph_optimize(randt_ctx* ctx, int n_poses, double* h_poses, int 
       if (++run > seg_cap) { is_sep[i] = 1; run = 0; }
     }
   }
-  std::vector<int32_t> int_of(n_poses, -1), sep_of(n_poses, -1), int_pose, sep_pose;
+  h.int_of.assign(n_poses, -1);
+  h.sep_of.assign(n_poses, -1);
   for (int i = 0; i < n_poses; ++i) {
     if (!is_var[i]) continue;
     if (is_sep[i]) {
-      sep_of[i] = (int)sep_pose.size();
-      sep_pose.push_back(i);
+      h.sep_of[i] = (int)h.sep_pose.size();
+      h.sep_pose.push_back(i);
     } else {
-      int_of[i] = (int)int_pose.size();
-      int_pose.push_back(i);
+      h.int_of[i] = (int)h.int_pose.size();
+      h.int_pose.push_back(i);
     }
   }
-  const int n_int = (int)int_pose.size(), n_sep = (int)sep_pose.size();
-  const int ns = 3 * n_sep;
-  if (out) out->n_separator_poses = n_sep;
-  if (n_sep > RANDT_PG_MAX_SEPARATORS)
-    return randt_set_error(ctx, RANDT_ERR_UNSUPPORTED, "pose graph: too many loop-closure poses for the dense Schur complement", hipSuccess);
-  std::vector<int32_t> seg_first, seg_len, bndL(n_int > 0 ? n_int : 1, -1), bndR(n_int > 0 ? n_int : 1, -1);
-  std::vector<int32_t> nbL(n_sep > 0 ? n_sep : 1, -1), nbR(n_sep > 0 ? n_sep : 1, -1);
+  h.n_int = (int)h.int_pose.size();
+  h.n_sep = (int)h.sep_pose.size();
+  h.ns = 3 * h.n_sep;
+}
+
+// Chain segments between separators and the incidence lists (ascending edge order per pose).
+void pg_segments(int n_poses, PgHost& h) {
+  const int nu = h.nu, n_int = h.n_int, n_sep = h.n_sep;
+  const std::vector<int32_t>&ia = h.ia, &ib = h.ib, &int_pose = h.int_pose, &sep_of = h.sep_of;
+  h.bndL.assign(n_int > 0 ? n_int : 1, -1);
+  h.bndR.assign(n_int > 0 ? n_int : 1, -1);
+  h.nbL.assign(n_sep > 0 ? n_sep : 1, -1);
+  h.nbR.assign(n_sep > 0 ? n_sep : 1, -1);
   for (int m = 0; m < n_int;) {
     int len = 1;
     while (m + len < n_int && int_pose[m + len] == int_pose[m + len - 1] + 1) ++len;
     const int vf = int_pose[m], vl = int_pose[m + len - 1];
     const int ql = (vf - 1 >= 0) ? sep_of[vf - 1] : -1, qr = (vl + 1 < n_poses) ? sep_of[vl + 1] : -1;
     for (int t = 0; t < len; ++t) {
-      bndL[m + t] = ql;
-      bndR[m + t] = qr;
+      h.bndL[m + t] = ql;
+      h.bndR[m + t] = qr;
     }
-    if (ql >= 0) nbR[ql] = m;
-    if (qr >= 0) nbL[qr] = m + len - 1;
-    seg_first.push_back(m);
-    seg_len.push_back(len);
+    if (ql >= 0) h.nbR[ql] = m;
+    if (qr >= 0) h.nbL[qr] = m + len - 1;
+    h.seg_first.push_back(m);
+    h.seg_len.push_back(len);
     m += len;
   }
-  const int n_seg = (int)seg_first.size();
-  // incidence lists (ascending edge order per pose)
-  std::vector<int32_t> inc_off(n_poses + 1, 0), inc_ent(2 * (size_t)nu);
+  h.n_seg = (int)h.seg_first.size();
+  h.inc_off.assign(n_poses + 1, 0);
+  h.inc_ent.resize(2 * (size_t)nu);
   for (int e = 0; e < nu; ++e) {
-    inc_off[ia[e] + 1]++;
-    inc_off[ib[e] + 1]++;
+    h.inc_off[ia[e] + 1]++;
+    h.inc_off[ib[e] + 1]++;
   }
-  for (int i = 0; i < n_poses; ++i) inc_off[i + 1] += inc_off[i];
+  for (int i = 0; i < n_poses; ++i) h.inc_off[i + 1] += h.inc_off[i];
   {
-    std::vector<int32_t> fill(inc_off.begin(), inc_off.end() - 1);
+    std::vector<int32_t> fill(h.inc_off.begin(), h.inc_off.end() - 1);
     for (int e = 0; e < nu; ++e) {
-      inc_ent[fill[ia[e]]++] = (e << 1) | 0;
-      inc_ent[fill[ib[e]]++] = (e << 1) | 1;
+      h.inc_ent[fill[ia[e]]++] = (e << 1) | 0;
+      h.inc_ent[fill[ib[e]]++] = (e << 1) | 1;
     }
   }
+}
 
-  // ---- device block
-  PgDev d{};
+#define PG_TRY(call)                                                                \
+  do {                                                                              \
+    hipError_t e__ = (call);                                                        \
+    if (e__ != hipSuccess && rc == RANDT_OK) rc = randt_set_error(ctx, RANDT_ERR_HIP, #call, e__); \
+  } while (0)
+
+// One device block from the context's storage pool (api.hip) carved into every array of PgDev, index tables and poses
+// uploaded.  with_cov adds what only the covariance path uses: the ns x ns inverse factor and the [n_poses][9] output.
+int pg_device_setup(randt_ctx* ctx, int n_poses, const PgHost& h, const double* h_poses, bool with_cov, PgDev& d, char** blk_out,
+                    size_t* blk_bytes_out) {
+  const int nu = h.nu, n_int = h.n_int, n_sep = h.n_sep, ns = h.ns, n_seg = h.n_seg;
   d.n_poses = n_poses; d.n_edges = nu; d.n_int = n_int; d.n_sep = n_sep; d.ns = ns; d.n_seg = n_seg;
   int32_t *d_ia, *d_ib, *d_inc_off, *d_inc_ent, *d_is_var, *d_int_of, *d_sep_of, *d_int_pose, *d_sep_pose, *d_seg_first, *d_seg_len, *d_bndL, *d_bndR,
       *d_nbL, *d_nbR;
@@ -821,12 +1043,18 @@ int randt_pose_graph_optimize(randt_ctx* ctx, int n_poses, double* h_poses, int 
     d.p_gabs = cv.take<double>(n_poses); d.p_xsq = cv.take<double>(n_poses); d.p_sn = cv.take<double>(n_poses);
     d.p_mcc = cv.take<double>(nu);
     d.scal = cv.take<double>(8); d.flags = cv.take<int32_t>(4);
+    if (with_cov) {
+      d.Mt = cv.take<double>((size_t)ns * ns);
+      d.cov = cv.take<double>(9 * (size_t)n_poses);
+    }
   };
   carve();  // sizing pass
   const size_t bytes = cv.off + 256;
   char* blk = nullptr;
   size_t blk_bytes = 0;
   RANDT_HIP_CHECK(ctx, randt_dev_alloc(ctx, reinterpret_cast<void**>(&blk), bytes, &blk_bytes));  // the context's storage pool (api.hip)
+  *blk_out = blk;
+  *blk_bytes_out = blk_bytes;
   cv = Carver{blk, 0};
   carve();
   d.ia = d_ia; d.ib = d_ib; d.meas = d_meas; d.sqi = d_sqi; d.inc_off = d_inc_off; d.inc_ent = d_inc_ent;
@@ -835,28 +1063,101 @@ int randt_pose_graph_optimize(randt_ctx* ctx, int n_poses, double* h_poses, int 
 
   hipStream_t st = ctx->stream;
   int rc = RANDT_OK;
-#define PG_TRY(call)                                                                \
-  do {                                                                              \
-    hipError_t e__ = (call);                                                        \
-    if (e__ != hipSuccess && rc == RANDT_OK) rc = randt_set_error(ctx, RANDT_ERR_HIP, #call, e__); \
-  } while (0)
 #define PG_UP(dst, vec, T) \
   if (!(vec).empty()) PG_TRY(hipMemcpyAsync((dst), (vec).data(), sizeof(T) * (vec).size(), hipMemcpyHostToDevice, st))
-  PG_UP(d_ia, ia, int32_t); PG_UP(d_ib, ib, int32_t); PG_UP(d_meas, meas, double); PG_UP(d_sqi, sqi, double);
-  PG_UP(d_inc_off, inc_off, int32_t); PG_UP(d_inc_ent, inc_ent, int32_t); PG_UP(d_is_var, is_var, int32_t);
-  PG_UP(d_int_of, int_of, int32_t); PG_UP(d_sep_of, sep_of, int32_t); PG_UP(d_int_pose, int_pose, int32_t);
-  PG_UP(d_sep_pose, sep_pose, int32_t);
+  PG_UP(d_ia, h.ia, int32_t); PG_UP(d_ib, h.ib, int32_t); PG_UP(d_meas, h.meas, double); PG_UP(d_sqi, h.sqi, double);
+  PG_UP(d_inc_off, h.inc_off, int32_t); PG_UP(d_inc_ent, h.inc_ent, int32_t); PG_UP(d_is_var, h.is_var, int32_t);
+  PG_UP(d_int_of, h.int_of, int32_t); PG_UP(d_sep_of, h.sep_of, int32_t); PG_UP(d_int_pose, h.int_pose, int32_t);
+  PG_UP(d_sep_pose, h.sep_pose, int32_t);
   if (n_int > 0) {
-    PG_UP(d_seg_first, seg_first, int32_t); PG_UP(d_seg_len, seg_len, int32_t); PG_UP(d_bndL, bndL, int32_t); PG_UP(d_bndR, bndR, int32_t);
+    PG_UP(d_seg_first, h.seg_first, int32_t); PG_UP(d_seg_len, h.seg_len, int32_t); PG_UP(d_bndL, h.bndL, int32_t); PG_UP(d_bndR, h.bndR, int32_t);
   }
   if (n_sep > 0) {
-    PG_UP(d_nbL, nbL, int32_t); PG_UP(d_nbR, nbR, int32_t);
+    PG_UP(d_nbL, h.nbL, int32_t); PG_UP(d_nbR, h.nbR, int32_t);
   }
 #undef PG_UP
   PG_TRY(hipMemcpyAsync(d.x, h_poses, sizeof(double) * 3 * (size_t)n_poses, hipMemcpyHostToDevice, st));
   PG_TRY(hipMemsetAsync(d.step, 0, sizeof(double) * 3 * (size_t)n_poses, st));
   // the host arrays above must outlive the copies
   PG_TRY(hipStreamSynchronize(st));
+  return rc;
+}
+
+// Factor of (H + D / radius) in the elimination order above: chain segments, their seven right-hand sides, the Schur
+// complement and its blocked dense Cholesky.  The caller has set flags to 1.
+void pg_factorize(hipStream_t st, const PgDev& d, double inv_radius) {
+  const int ns = d.ns;
+  if (d.n_int > 0) {
+    hipLaunchKernelGGL(k_pg_factor, dim3(grid_for(d.n_seg, 64)), dim3(64), 0, st, d, inv_radius);
+    hipLaunchKernelGGL(k_pg_chain_solve, dim3(grid_for((size_t)d.n_seg * 8, 64)), dim3(64), 0, st, d);
+  }
+  if (ns > 0) {
+    hipLaunchKernelGGL(k_pg_schur, dim3(grid_for((size_t)(ns + 1) * ns, 256)), dim3(256), 0, st, d, inv_radius);
+    for (int k0 = 0; k0 < ns; k0 += PG_NB) {
+      const int nb = std::min(PG_NB, ns - k0), below = ns - (k0 + nb) + 1;  // rows under the block, RHS row included
+      hipLaunchKernelGGL(k_pg_potrf, dim3(1), dim3(PG_NB * PG_NB), 0, st, d, k0);
+      hipLaunchKernelGGL(k_pg_trsm, dim3(grid_for(below, 64)), dim3(256), 0, st, d, k0);
+      const int tiles = (below + 63) / 64;
+      hipLaunchKernelGGL(k_pg_syrk, dim3(tiles * (tiles + 1) / 2), dim3(256), 0, st, d, k0);
+    }
+  }
+}
+
+}  // namespace
+
+void randt_pg_params_default(randt_pg_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->use_robust_loss = 0;
+  p->loss_scale = 60.0;
+  p->max_iterations = 200000;  // global_fuser.cpp:52
+  p->max_consecutive_invalid_steps = 5;
+  p->function_tolerance = 1e-6;
+  p->gradient_tolerance = 1e-10;
+  p->parameter_tolerance = 1e-8;
+  p->initial_radius = 1e4;
+  p->max_radius = 1e16;
+  p->min_radius = 1e-32;
+  p->min_relative_decrease = 1e-3;
+  p->min_lm_diagonal = 1e-6;
+  p->max_lm_diagonal = 1e32;
+}
+
+int randt_pose_graph_optimize(randt_ctx* ctx, int n_poses, double* h_poses, int n_edges, const int32_t* h_id_begin,
+                                         const int32_t* h_id_end, const double* h_meas, const double* h_sqrt_info,
+                                         int max_update_index, const randt_pg_params* opt, randt_pg_result* out) {
+  DeviceGuard dev_guard__(ctx);
+  if (!ctx || !opt || n_poses <= 0 || n_edges < 0 || !h_poses) return RANDT_ERR_INVALID;
+  if (n_edges > 0 && (!h_id_begin || !h_id_end || !h_meas || !h_sqrt_info)) return RANDT_ERR_INVALID;
+  if (out) {
+    memset(out, 0, sizeof(*out));
+    out->n_loop_closures = n_edges + 1 - n_poses;  // global_fuser.cpp:26
+  }
+  PgHost h;
+  if (int frc = pg_filter_edges(ctx, n_poses, n_edges, h_id_begin, h_id_end, h_meas, h_sqrt_info, max_update_index, 0, h)) return frc;
+  const int nu = h.nu;
+  if (out) out->n_residual_blocks = nu;
+  if (nu == 0 || h.n_var == 0) return RANDT_OK;
+  pg_order(n_poses, h);
+  const int n_int = h.n_int, n_sep = h.n_sep, ns = h.ns;
+  if (out) out->n_separator_poses = n_sep;
+  if (n_sep > RANDT_PG_MAX_SEPARATORS)
+    return randt_set_error(ctx, RANDT_ERR_UNSUPPORTED, "pose graph: too many loop-closure poses for the dense Schur complement", hipSuccess);
+  pg_segments(n_poses, h);
+  const int n_seg = h.n_seg;
+
+  PgDev d{};
+  char* blk = nullptr;
+  size_t blk_bytes = 0;
+  int rc = pg_device_setup(ctx, n_poses, h, h_poses, false, d, &blk, &blk_bytes);
+  if (rc != RANDT_OK) {
+    if (blk) {
+      (void)randt_sync(ctx);
+      randt_dev_release(ctx, blk, blk_bytes);
+    }
+    return rc;
+  }
+  hipStream_t st = ctx->stream;
 
   const int robust = opt->use_robust_loss ? 1 : 0;
   double h_scal[8];
@@ -915,21 +1216,8 @@ int randt_pose_graph_optimize(randt_ctx* ctx, int n_poses, double* h_poses, int 
       hipLaunchKernelGGL(k_pg_lm_diagonal, dim3(grid_for(n_poses, 256)), dim3(256), 0, st, d, opt->min_lm_diagonal, opt->max_lm_diagonal);
     const double inv_radius = 1.0 / radius;
     PG_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.flags), 1, 4, st));
-    if (n_int > 0) {
-      hipLaunchKernelGGL(k_pg_factor, dim3(grid_for(n_seg, 64)), dim3(64), 0, st, d, inv_radius);
-      hipLaunchKernelGGL(k_pg_chain_solve, dim3(grid_for((size_t)n_seg * 8, 64)), dim3(64), 0, st, d);
-    }
-    if (ns > 0) {
-      hipLaunchKernelGGL(k_pg_schur, dim3(grid_for((size_t)(ns + 1) * ns, 256)), dim3(256), 0, st, d, inv_radius);
-      for (int k0 = 0; k0 < ns; k0 += PG_NB) {
-        const int nb = std::min(PG_NB, ns - k0), below = ns - (k0 + nb) + 1;  // rows under the block, RHS row included
-        hipLaunchKernelGGL(k_pg_potrf, dim3(1), dim3(PG_NB * PG_NB), 0, st, d, k0);
-        hipLaunchKernelGGL(k_pg_trsm, dim3(grid_for(below, 64)), dim3(256), 0, st, d, k0);
-        const int tiles = (below + 63) / 64;
-        hipLaunchKernelGGL(k_pg_syrk, dim3(tiles * (tiles + 1) / 2), dim3(256), 0, st, d, k0);
-      }
-      hipLaunchKernelGGL(k_pg_trsv, dim3(1), dim3(1024), 0, st, d);
-    }
+    pg_factorize(st, d, inv_radius);
+    if (ns > 0) hipLaunchKernelGGL(k_pg_trsv, dim3(1), dim3(1024), 0, st, d);
     hipLaunchKernelGGL(k_pg_backsub, dim3(grid_for(n_int + n_sep, 256)), dim3(256), 0, st, d);
     hipLaunchKernelGGL(k_pg_candidate, dim3(grid_for(n_poses, 256)), dim3(256), 0, st, d);
     hipLaunchKernelGGL(k_pg_mcc, dim3(grid_for(nu, 256)), dim3(256), 0, st, d, cur);
@@ -984,7 +1272,6 @@ int randt_pose_graph_optimize(randt_ctx* ctx, int n_poses, double* h_poses, int 
       summary_min_cost = std::min(summary_min_cost, cand_cost);
     }
   }
-#undef PG_TRY
   (void)randt_sync(ctx);
   randt_dev_release(ctx, blk, blk_bytes);
   if (rc != RANDT_OK) return rc;
@@ -996,3 +1283,77 @@ int randt_pose_graph_optimize(randt_ctx* ctx, int n_poses, double* h_poses, int 
   }
   return RANDT_OK;
 }
+
+int randt_pose_graph_covariance(randt_ctx* ctx, int n_poses, const double* h_poses, int n_edges, const int32_t* h_id_begin,
+                                const int32_t* h_id_end, const double* h_meas, const double* h_sqrt_info, int max_update_index,
+                                const randt_pg_params* opt, int anchor_pose, double* h_cov) {
+  DeviceGuard dev_guard__(ctx);
+  if (!ctx || !opt || n_poses <= 0 || n_edges < 0 || !h_poses || !h_cov) return RANDT_ERR_INVALID;
+  if (n_edges > 0 && (!h_id_begin || !h_id_end || !h_meas || !h_sqrt_info)) return RANDT_ERR_INVALID;
+  const int anchor = anchor_pose == -1 ? n_poses - 1 : anchor_pose;  // global_fuser.cpp:68-69 fixes the LAST pose
+  if (anchor < 0 || anchor >= n_poses) return randt_set_error(ctx, RANDT_ERR_INVALID, "pose graph covariance: anchor pose out of range", hipSuccess);
+  PgHost h;
+  if (int frc = pg_filter_edges(ctx, n_poses, n_edges, h_id_begin, h_id_end, h_meas, h_sqrt_info, max_update_index, anchor, h)) return frc;
+  const int nu = h.nu;
+  if (nu == 0 || h.n_var == 0) {
+    memset(h_cov, 0, sizeof(double) * 9 * (size_t)n_poses);
+    return RANDT_OK;
+  }
+  {  // every variable pose must reach the anchor through used edges, otherwise H has a null space (a free rigid motion)
+    std::vector<int32_t> comp(n_poses);
+    for (int i = 0; i < n_poses; ++i) comp[i] = i;
+    auto find = [&](int i) {
+      while (comp[i] != i) i = comp[i] = comp[comp[i]];
+      return i;
+    };
+    for (int e = 0; e < nu; ++e) comp[find(h.ia[e])] = find(h.ib[e]);
+    const int root = find(anchor);
+    for (int i = 0; i < n_poses; ++i)
+      if (h.is_var[i] && find(i) != root)
+        return randt_set_error(ctx, RANDT_ERR_INVALID, "pose graph covariance: rank deficient (a variable pose is not connected to the anchor)", hipSuccess);
+  }
+  pg_order(n_poses, h);
+  const int n_int = h.n_int, n_sep = h.n_sep, ns = h.ns;
+  if (n_sep > RANDT_PG_MAX_SEPARATORS)
+    return randt_set_error(ctx, RANDT_ERR_UNSUPPORTED, "pose graph: too many loop-closure poses for the dense Schur complement", hipSuccess);
+  pg_segments(n_poses, h);
+
+  PgDev d{};
+  char* blk = nullptr;
+  size_t blk_bytes = 0;
+  int rc = pg_device_setup(ctx, n_poses, h, h_poses, true, d, &blk, &blk_bytes);
+  hipStream_t st = ctx->stream;
+  std::vector<double> cov(9 * (size_t)n_poses);
+  int32_t h_flags[4] = {0, 0, 0, 0};
+  if (rc == RANDT_OK) {
+    // linearise at h_poses exactly as the optimiser does (Jacobi scaling included), then factor WITHOUT damping:
+    // inv_radius = 0 multiplies the LM diagonal, which only has to be finite
+    PG_TRY(hipMemsetAsync(d.diagonal, 0, sizeof(double) * 3 * (size_t)n_poses, st));
+    hipLaunchKernelGGL(k_pg_edges, dim3(grid_for(nu, 256)), dim3(256), 0, st, d, d.x, 0, opt->use_robust_loss ? 1 : 0, opt->loss_scale);
+    hipLaunchKernelGGL(k_pg_pose_diag, dim3(grid_for(n_poses, 256)), dim3(256), 0, st, d, 0, 1);
+    if (ns > 0) PG_TRY(hipMemsetAsync(d.S0, 0, sizeof(double) * (size_t)ns * ns, st));
+    hipLaunchKernelGGL(k_pg_pose_offdiag, dim3(grid_for(n_poses, 256)), dim3(256), 0, st, d, 0);
+    PG_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.flags), 1, 4, st));
+    pg_factorize(st, d, 0.0);
+    if (ns > 0) {
+      hipLaunchKernelGGL(k_pg_cov_trinv, dim3((ns + PG_NB - 1) / PG_NB, PG_NB / 8), dim3(256), 0, st, d);
+      hipLaunchKernelGGL(k_pg_cov_sep_blocks, dim3(n_sep + h.n_seg), dim3(256), 0, st, d);
+    }
+    if (n_int > 0) hipLaunchKernelGGL(k_pg_cov_chain, dim3(grid_for(h.n_seg, 64)), dim3(64), 0, st, d);
+    hipLaunchKernelGGL(k_pg_cov_gather, dim3(grid_for(n_poses, 256)), dim3(256), 0, st, d);
+    PG_TRY(hipMemcpyAsync(cov.data(), d.cov, sizeof(double) * cov.size(), hipMemcpyDeviceToHost, st));
+    PG_TRY(hipMemcpyAsync(h_flags, d.flags, sizeof(h_flags), hipMemcpyDeviceToHost, st));
+    PG_TRY(hipStreamSynchronize(st));
+    PG_TRY(hipGetLastError());
+  }
+  if (blk) {
+    (void)randt_sync(ctx);
+    randt_dev_release(ctx, blk, blk_bytes);
+  }
+  if (rc != RANDT_OK) return rc;
+  if (!(h_flags[0] && h_flags[1] && h_flags[2]))
+    return randt_set_error(ctx, RANDT_ERR_INVALID, "pose graph covariance: rank deficient (the undamped factorisation broke down)", hipSuccess);
+  memcpy(h_cov, cov.data(), sizeof(double) * cov.size());
+  return RANDT_OK;
+}
+#undef PG_TRY

@@ -585,6 +585,25 @@ def pose_graph_optimize(ctx, poses, id_begin, id_end, meas, sqrt_info, max_updat
     return x, {k: getattr(res, k) for k, _ in PgResult._fields_}
 
 
+def pose_graph_covariance(ctx, poses, id_begin, id_end, meas, sqrt_info, max_update_index, params=None, anchor=-1):
+    """randt_pose_graph_covariance: the 3x3 marginal covariance (x, y, yaw) of every pose at `poses`, pose `anchor` held
+    constant (-1 = the last one, global_fuser.cpp:68-69).  Same edge arrays as pose_graph_optimize; of params only
+    use_robust_loss / loss_scale are read.  Returns [N][3][3]; the anchor's and untouched poses' blocks are zero."""
+    x = np.array(poses, dtype=np.float64, order="C").reshape(-1, 3)
+    ia = np.ascontiguousarray(id_begin, dtype=np.int32)
+    ib = np.ascontiguousarray(id_end, dtype=np.int32)
+    m = np.ascontiguousarray(meas, dtype=np.float64).reshape(-1, 3)
+    sq = np.ascontiguousarray(sqrt_info, dtype=np.float64).reshape(-1, 9)
+    if not (len(ia) == len(ib) == len(m) == len(sq)):
+        raise ValueError("edge arrays differ in length")
+    p = params if params is not None else pg_params()
+    cov = np.zeros((len(x), 3, 3))
+    ctx._check(ctx._lib.randt_pose_graph_covariance(ctx._h, len(x), x.ctypes.data, len(ia), ia.ctypes.data, ib.ctypes.data, m.ctypes.data,
+                                                    sq.ctypes.data, int(max_update_index), C.byref(p), int(anchor), cov.ctypes.data),
+               "randt_pose_graph_covariance")
+    return cov
+
+
 # ------------------------------------------------------------------ Scan Context (f-4) --------------
 def sc_params(num_ring=20, num_sector=45, max_radius=15.0, num_exclude_recent=15, num_candidates=10, search_ratio=0.3,
               dist_thresh=0.6, assumed_drift=0.05, odom_eps=1.2, odom_weight=0.2, intensity_factor=0.04):

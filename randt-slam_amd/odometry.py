@@ -144,6 +144,15 @@ class HipBackend:
     def pose_graph_optimize(self, x, ia, ib, meas, sqi, max_update_index, params_kwargs):
         return host.pose_graph_optimize(self.ctx, x, ia, ib, meas, sqi, max_update_index, host.pg_params(**params_kwargs))
 
+    def pose_graph_covariance(self, x, ia, ib, meas, sqi, max_update_index, params_kwargs, anchor=-1):
+        return host.pose_graph_covariance(self.ctx, x, ia, ib, meas, sqi, max_update_index, host.pg_params(**params_kwargs), anchor)
+
+    def search_global(self, sub_idx, scan_idx, mp, bp, guess4, scale, window_linear, window_angular):
+        """Matcher::estimateTransformGlobalBNB: submap (fixed) vs scan (moving); returns the best pose4."""
+        bp = host.bnb_params() if bp is None else bp
+        _, p, _ = host.search_global(self.ctx, self.subs, sub_idx, self.scans, scan_idx, mp, bp, guess4, scale, window_linear, window_angular)
+        return p
+
     def register_window(self, fixed_idx, moving_idx, states, mp, wp, trans4, imu=None):
         st, t, rej, res = host.register_window(self.ctx, self.subs, fixed_idx, self.scans, moving_idx, states, mp, wp, trans4, imu)
         return st, t, rej, res

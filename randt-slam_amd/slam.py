@@ -1,6 +1,7 @@
 """The reference's full SLAM loop as a call-pattern harness (row f-4): LocalFuser::processScan's graph bookkeeping
 (src/local_fuser/local_fuser.cpp:164-223 keyframe node + odometry edge, :247-279 submap root node),
-LocalFuser::detectLoopClosures (:318-410, Scan Context branch), NDTSlam::optimizePoseGraph (src/ndt_slam/ndt_slam.cpp:
+LocalFuser::detectLoopClosures (:318-416: the Scan Context branch, and -- loop_search="covariance" -- the branch gated by the
+nodes' marginal covariances, :351-412, dead in the reference since its covariance block is commented out), NDTSlam::optimizePoseGraph (src/ndt_slam/ndt_slam.cpp:
 351-361 -> GlobalFuser::optimizePoseGraph) and the pose part of LocalFuser::updateSubmaps (:65-88).
 
 Everything numeric goes through the injected backend (odometry.HipBackend = the C ABI: NDT build, window registration,
@@ -24,17 +25,43 @@ def _angle(p4):
     return math.atan2(p4[1], p4[0])                    # so2().log()
 
 
+def _mahalanobis2(cov, dx, dy):
+    """sqrt(d^T cov_pos_pos^-1 d) with the closed-form 2x2 inverse, or None if cov_pos_pos is not positive definite."""
+    a, b, c, d = cov[0, 0], cov[0, 1], cov[1, 0], cov[1, 1]
+    det = a * d - b * c
+    if not (a > 0.0 and det > 0.0):
+        return None
+    return math.sqrt((d * dx * dx - (b + c) * dx * dy + a * dy * dy) / det)
+
+
+def _smaller_eigenvalue2(cov):
+    """Smaller eigenvalue of the self-adjoint xy block (lower triangle read, like Eigen::SelfAdjointEigenSolver)."""
+    a, c, d = cov[0, 0], cov[1, 0], cov[1, 1]
+    return 0.5 * (a + d) - math.sqrt(0.25 * (a - d) * (a - d) + c * c)
+
+
 class Slam(Odometry):
     keep_filtered_points = True
 
     def __init__(self, backend, matcher_params, window_params, loop_matcher_params, params=None, sc_params=None,
-                 loop_closure_max_cs_divergence=3.6, loop_closure_weight=4.0e4, loop_sqrtI=None, pg_params=None):
+                 loop_closure_max_cs_divergence=3.6, loop_closure_weight=4.0e4, loop_sqrtI=None, pg_params=None,
+                 loop_search="scan_context", max_data_association_mahalanobis_dist=0.5, compute_dfs_loop_closure=False,
+                 bnb_params=None, bnb_matcher_params=None, loop_closure_scale=1.5):
         super().__init__(backend, matcher_params, window_params, params)
+        if loop_search not in ("scan_context", "covariance"):
+            raise ValueError("loop_search must be 'scan_context' or 'covariance'")
+        self.loop_search = loop_search
+        self.max_mahalanobis = float(max_data_association_mahalanobis_dist)   # base yaml :26
+        self.compute_dfs = bool(compute_dfs_loop_closure)                     # base yaml :25
+        self.bnb_params = bnb_params                                          # csm_* of the matcher (backend default if None)
+        self.bnb_mp = bnb_matcher_params if bnb_matcher_params is not None else loop_matcher_params
+        self.loop_scale = float(loop_closure_scale)
         self.loop_mp = loop_matcher_params
         self.max_cs = loop_closure_max_cs_divergence   # parameters_indoor.yaml:8
         self.loop_sqrt_info = loop_closure_weight * (np.eye(3) if loop_sqrtI is None else np.asarray(loop_sqrtI, dtype=np.float64))
         self.pg_params = dict(pg_params or {})
-        backend.sc_open(dict(sc_params or {}))
+        if loop_search == "scan_context":
+            backend.sc_open(dict(sc_params or {}))
         self.nodes = []                # global pose4 per node id (std::map<int, Pose>, keys 0..n-1)
         self.traversed = []            # Pose::traversed_dist
         self.edges = []                # (id_begin, id_end, trans pose4, sqrt_information 3x3)
@@ -45,6 +72,8 @@ class Slam(Odometry):
         self.pending_loop_search = []  # _next_maps_to_search_loop
         self.loop_log = []             # (query node, candidate node, cs divergence, accepted)
         self.n_optimizations = 0
+        self.node_cov = []             # covariance mode: Pose::cov per node (3x3, zeros until an optimisation covered the node)
+        self.n_covariance_failures = 0
 
     # ---- graph bookkeeping ------------------------------------------------------------------
     def _add_node(self, pose4, scan, points):
@@ -60,7 +89,9 @@ class Slam(Odometry):
         self.submap_idzs.append(self.n_finished_submaps)
         self.node_scans[nid] = scan
         self._ref(scan)
-        self.b.sc_append(points, pose4[2:], dist)                                         # :207, :281
+        self.node_cov.append(np.zeros((3, 3)))
+        if self.loop_search == "scan_context":
+            self.b.sc_append(points, pose4[2:], dist)                                     # :207, :281
         return nid
 
     def _on_first_scan(self, scan, points):
@@ -77,6 +108,8 @@ class Slam(Odometry):
 
     # ---- LocalFuser::detectLoopClosures, Scan Context branch (:318-350) ------------------------
     def detect_loop_closures(self):
+        if self.loop_search == "covariance":
+            return self._detect_loop_closures_covariance()
         added = 0
         while self.pending_loop_search:
             q = self.pending_loop_search.pop(0)
@@ -97,6 +130,43 @@ class Slam(Odometry):
                 added += 1
         return added
 
+    # ---- LocalFuser::detectLoopClosures, the branch without Scan Context (:351-412), quirks included -------
+    def _detect_loop_closures_covariance(self):
+        added = 0
+        thr = self.max_mahalanobis
+        while self.pending_loop_search:
+            q = self.pending_loop_search.pop(0)
+            best = {}                                  # submap -> (node, dist): the closest node of every finished submap
+            tq = self.nodes[q]
+            for i in range(len(self.nodes)):
+                sub_i = self.submap_idzs[i]
+                if sub_i == self.submap_idzs[q] or sub_i == self.n_finished_submaps or sub_i not in self.submaps:   # :355
+                    continue
+                dist = _mahalanobis2(self.node_cov[i], tq[2] - self.nodes[i][2], tq[3] - self.nodes[i][3])           # :357, the NODE's covariance
+                if dist is None:                       # never covered by an optimisation (the reference: NaN < thr is false)
+                    continue
+                if dist < thr and (sub_i not in best or dist < best[sub_i][1]):                                     # :358-362
+                    best[sub_i] = (i, dist)
+            for sub_i in sorted(best):                 # std::map order
+                lid = best[sub_i][0]
+                root = self.nodes[self.root_nodes[sub_i]]
+                guess = _se2_mul4(_se2_inv4(root), tq)                                                              # :376
+                if self.compute_dfs:                                                                                # :379-388
+                    cov = self.node_cov[lid]
+                    lam0 = _smaller_eigenvalue2(cov)   # eigenvalues()(0): the SMALLER one, named "max" there, no root taken
+                    window_linear = thr * abs(lam0)
+                    window_angular = min(2 * math.pi, thr * math.sqrt(cov[2, 2]))
+                    guess = self.b.search_global(self.submaps[sub_i], self.node_scans[q], self.bnb_mp, self.bnb_params, guess,
+                                                 self.loop_scale, window_linear, window_angular)
+                est, _cost = self.b.register_pair(self.submaps[sub_i], self.node_scans[q], self.loop_mp, guess)     # :395
+                cs = self.b.cs_divergence(self.submaps[sub_i], self.node_scans[q], est)                             # :396-397
+                ok = bool(cs < self.max_cs)
+                self.loop_log.append((q, lid, float(cs), ok))
+                if ok:
+                    self.edges.append((self.root_nodes[sub_i], q, np.array(est, dtype=np.float64), self.loop_sqrt_info))   # :402-409
+                    added += 1
+        return added
+
     # ---- NDTSlam::optimizePoseGraph (ndt_slam.cpp:351-361) --------------------------------------
     def optimize_pose_graph(self):
         if not self.nodes or not self.edges or self.submap_idzs[-1] <= 0:
@@ -109,6 +179,18 @@ class Slam(Odometry):
         meas = np.array([[e[2][2], e[2][3], _angle(e[2])] for e in self.edges])
         sqi = np.array([e[3] for e in self.edges])
         xo, res = self.b.pose_graph_optimize(x, ia, ib, meas, sqi, max_update_index, self.pg_params)
+        if self.loop_search == "covariance":
+            # the ceres::Covariance block of global_fuser.cpp:62-87: at the optimised poses, the LAST pose constant (:68-69)
+            try:
+                cov = self.b.pose_graph_covariance(xo, ia, ib, meas, sqi, max_update_index, self.pg_params, -1)
+            except Exception as e:                     # poses are still written back, covariances stay as they were
+                self.n_covariance_failures += 1
+                print("WARNING: pose graph covariance failed: %s" % e)
+                cov = None
+            if cov is not None:
+                for i in range(len(self.nodes)):
+                    c = cov[i]                         # cov_pos_pos, cov_pos_rot, cov_rot_rot -> Pose::cov (:86-89)
+                    self.node_cov[i] = np.array([[c[0, 0], c[0, 1], c[0, 2]], [c[1, 0], c[1, 1], c[1, 2]], [c[0, 2], c[1, 2], c[2, 2]]])
         for i in range(len(self.nodes)):
             self.nodes[i] = _pose4(xo[i, 2], xo[i, 0], xo[i, 1])                          # Sophus::SE2d(rot, pos), global_fuser.cpp:85
         # LocalFuser::updateSubmaps (:65-88), pose part: the current submap's origin follows its root node
