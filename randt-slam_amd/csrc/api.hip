@@ -156,6 +156,53 @@ void randt_dev_release(randt_ctx* ctx, void* p, size_t bytes) {
   ctx->pool_bytes += bytes;
 }
 
+// The ONE growth policy of the five scratch buffers: a request beyond the buffer drains the stream (which may still use the old
+// one), frees it and allocates a quarter more than asked + 4 KB, so that sizes creeping up from call to call settle after a
+// few steps.  Device buffers are counted (randt_ctx_pool_stats); a failed allocation leaves the buffer empty.
+int randt_scratch_reserve(randt_ctx* ctx, Scratch& s, size_t bytes) {
+  if (bytes <= s.bytes) return RANDT_OK;
+  if (s.p) {
+    RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+    void* old = s.p;
+    s.p = nullptr;
+    s.bytes = 0;
+    RANDT_HIP_CHECK(ctx, s.pinned ? hipHostFree(old) : randt_hip_free(ctx, old));
+  }
+  const size_t want = bytes + bytes / 4 + 4096;
+  const hipError_t e = s.pinned ? hipHostMalloc(&s.p, want, hipHostMallocDefault) : randt_hip_malloc(ctx, &s.p, want);
+  if (e != hipSuccess) {
+    s.p = nullptr;
+    return randt_set_error(ctx, RANDT_ERR_HIP, "scratch allocation", e);
+  }
+  s.bytes = want;
+  return RANDT_OK;
+}
+
+SolveParams randt_solve_params(const randt_matcher_params* mp) {
+  SolveParams P;
+  P.loss_a = mp->loss_scale;
+  P.mu_scale = mp->mu_scale;
+  P.alpha = mp->loss_alpha;
+  P.weight = mp->loss_weight;
+  P.gnc_div = mp->gnc_divisor;
+  P.mu_cap = pow(mp->gnc_divisor, (double)(mp->gnc_steps - 1));
+  P.mu_stop = 1.0 / sqrt(mp->gnc_divisor);
+  P.ftol = mp->function_tolerance;
+  P.gtol = mp->gradient_tolerance;
+  P.ptol = mp->parameter_tolerance;
+  P.r0 = mp->initial_radius;
+  P.rmax = mp->max_radius;
+  P.rmin = mp->min_radius;
+  P.min_rel = mp->min_relative_decrease;
+  P.dmin = mp->min_lm_diagonal;
+  P.dmax = mp->max_lm_diagonal;
+  P.gnc_steps = mp->gnc_steps;
+  P.max_it = mp->max_iterations;
+  P.k = mp->n_neighbours;
+  P.max_invalid = mp->max_consecutive_invalid_steps;
+  return P;
+}
+
 void* randt_pin_take(randt_ctx* ctx, size_t bytes) {
   bytes = (bytes + 63) & ~(size_t)63;
   if (bytes > randt_ctx::kPinSegBytes) return nullptr;
@@ -199,18 +246,29 @@ void* randt_pin_take(randt_ctx* ctx, size_t bytes) {
 
 namespace {
 
-int ensure_ws(randt_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->ws_bytes) return RANDT_OK;
-  if (ctx->ws) {
-    RANDT_HIP_CHECK(ctx, randt_sync(ctx));
-    RANDT_HIP_CHECK(ctx, randt_hip_free(ctx, ctx->ws));
-    ctx->ws = nullptr;
-    ctx->ws_bytes = 0;
-  }
-  size_t want = bytes + bytes / 4 + 4096;
-  RANDT_HIP_CHECK(ctx, randt_hip_malloc(ctx, &ctx->ws, want));
-  ctx->ws_bytes = want;
-  return RANDT_OK;
+// A pooled block / a temporary batch that goes back at scope exit, so that the entry points holding one can return early.  No
+// synchronisation: whatever takes the block next is enqueued on the same stream, behind the work that still uses it.
+struct PooledBlock {
+  randt_ctx* ctx;
+  void* p = nullptr;
+  size_t bytes = 0;
+  explicit PooledBlock(randt_ctx* c) : ctx(c) {}
+  ~PooledBlock() { randt_dev_release(ctx, p, bytes); }
+  PooledBlock(const PooledBlock&) = delete;
+  PooledBlock& operator=(const PooledBlock&) = delete;
+  hipError_t alloc(size_t n) { return randt_dev_alloc(ctx, &p, n, &bytes); }
+};
+struct TmpMaps {
+  randt_maps* m = nullptr;
+  TmpMaps() = default;
+  ~TmpMaps() { (void)randt_maps_destroy(m); }
+  TmpMaps(const TmpMaps&) = delete;
+  TmpMaps& operator=(const TmpMaps&) = delete;
+};
+// a launch failed: the stream is drained before the entry point reports it
+int drained(randt_ctx* ctx, int rc) {
+  (void)randt_sync(ctx);
+  return rc;
 }
 
 void fill_view(randt_maps* m, int n_maps, const randt_map_params* p, int cap) {
@@ -479,12 +537,9 @@ int randt_ctx_destroy(randt_ctx* ctx) {
     for (int i = 0; i < randt_ctx::kPinSegs; ++i)
       if (ctx->pin_ev[i]) (void)hipEventDestroy(ctx->pin_ev[i]);
   }
-  if (ctx->ws) (void)hipFree(ctx->ws);
-  if (ctx->order_ws) (void)hipFree(ctx->order_ws);
-  if (ctx->build_ws) (void)hipFree(ctx->build_ws);
-  if (ctx->build_wide_ws) (void)hipFree(ctx->build_wide_ws);
+  for (Scratch* s : {&ctx->ws, &ctx->h_pin, &ctx->build_ws, &ctx->build_wide_ws, &ctx->order_ws})
+    if (s->p) (void)(s->pinned ? hipHostFree(s->p) : hipFree(s->p));
   if (ctx->small) (void)hipFree(ctx->small);
-  if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->marker_ev) (void)hipEventDestroy(ctx->marker_ev);
   if (ctx->misrank_word) (void)hipHostFree(ctx->misrank_word);
   if (ctx->d_misrank_count) (void)hipFree(ctx->d_misrank_count);
@@ -492,11 +547,11 @@ int randt_ctx_destroy(randt_ctx* ctx) {
   return RANDT_OK;
 }
 
-// 4 KB that the synchronous host-level entries carve their pose / index / result words from (they synchronise before
-// returning, so one block per context is enough and nothing is allocated per call).
-static int small_block(randt_ctx* ctx, char** out) {
-  if (!ctx->small) RANDT_HIP_CHECK(ctx, randt_hip_malloc(ctx, &ctx->small, 4096));
-  *out = static_cast<char*>(ctx->small);
+// The pose / index / result words of the synchronous host-level entries (they synchronise before returning, so one block
+// per context is enough and nothing is allocated per call).
+static int small_block(randt_ctx* ctx, SmallScratch** out) {
+  if (!ctx->small) RANDT_HIP_CHECK(ctx, randt_hip_malloc(ctx, reinterpret_cast<void**>(&ctx->small), sizeof(SmallScratch)));
+  *out = ctx->small;
   return RANDT_OK;
 }
 
@@ -555,28 +610,26 @@ int randt_maps_create_external(randt_ctx* ctx, int n_maps, const randt_map_param
   return RANDT_OK;
 }
 
-// Layout of a library-owned batch inside its ONE pooled block: [cells | counts | deferred status (2 words) | grid].
-static void block_layout(int n_maps, const randt_map_params* p, int cell_capacity, int with_grid, size_t* off_counts, size_t* off_grid,
-                         size_t* total) {
-  const size_t cb = (randt_maps_cells_bytes(n_maps, cell_capacity) + 255) & ~(size_t)255;
-  const size_t nb = (sizeof(int32_t) * ((size_t)n_maps + 2) + 255) & ~(size_t)255;
-  *off_counts = cb;
-  *off_grid = cb + nb;
-  *total = cb + nb + (with_grid ? ((randt_maps_grid_bytes(n_maps, p) + 255) & ~(size_t)255) : 0);
+// Layout of a library-owned batch inside its ONE pooled block: [cells | counts | deferred status (2 words) | grid], each
+// part starting on a 256-byte boundary.
+struct BlockLayout { randt_cell* cells; int32_t *counts, *grid; };
+static BlockLayout block_layout(Carve& c, int n_maps, const randt_map_params* p, int cell_capacity, int with_grid) {
+  return {c.take<randt_cell>((size_t)n_maps * cell_capacity), c.take<int32_t>((size_t)n_maps + 2),
+          with_grid ? c.take<int32_t>((size_t)n_maps * p->size_x * p->size_y) : nullptr};
 }
 
 // a batch on pooled storage, contents undefined (create clears it, clone copies into it)
 static int maps_alloc(randt_ctx* ctx, int n_maps, const randt_map_params* p, int cell_capacity, int with_grid, randt_maps** out) {
-  size_t off_counts, off_grid, total, granted = 0;
-  block_layout(n_maps, p, cell_capacity, with_grid, &off_counts, &off_grid, &total);
+  size_t granted = 0;
   void* blk = nullptr;
-  const hipError_t e = randt_dev_alloc(ctx, &blk, total, &granted);
+  const hipError_t e = randt_dev_alloc(ctx, &blk, carved_size([&](Carve& c) { block_layout(c, n_maps, p, cell_capacity, with_grid); }), &granted);
   if (e != hipSuccess) {
     (void)hipGetLastError();  // a failed hipMalloc leaves a sticky last-error; nothing else was allocated
     return randt_set_error(ctx, e == hipErrorOutOfMemory ? RANDT_ERR_NOMEM : RANDT_ERR_HIP, "hipMalloc (map storage)", e);
   }
-  char* b = static_cast<char*>(blk);
-  const int rc = randt_maps_create_external(ctx, n_maps, p, cell_capacity, b, b + off_counts, with_grid ? b + off_grid : nullptr, out);
+  Carve c(blk);
+  const BlockLayout L = block_layout(c, n_maps, p, cell_capacity, with_grid);
+  const int rc = randt_maps_create_external(ctx, n_maps, p, cell_capacity, L.cells, L.counts, L.grid, out);
   if (rc) {
     randt_dev_release(ctx, blk, granted);
     return rc;
@@ -835,19 +888,49 @@ int randt_ndt_build_pndt_batch_dev(randt_ctx* ctx, const float* d_points, int n_
                           d_polar, beam_cov9);
 }
 
-// host points -> the context's workspace without a synchronisation: through the pinned ring when they fit a segment (one
-// memcpy + one async DMA; the host buffer is free on return), a pageable copy + wait otherwise
-static int stage_points(randt_ctx* ctx, const float* h_points, size_t bytes, size_t ws_extra, const float** d_points) {
-  int rc = ensure_ws(ctx, bytes + ws_extra);
-  if (rc) return rc;
-  if (void* pin = randt_pin_take(ctx, bytes)) {
-    memcpy(pin, h_points, bytes);
-    RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->ws, pin, bytes, hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->ws, h_points, bytes, hipMemcpyHostToDevice, ctx->stream));
-    RANDT_HIP_CHECK(ctx, randt_sync(ctx));  // a pageable source of this size may still be read after the call returns
+// Host bytes -> somewhere this stream can read them.  `spans` make up one image of `total` bytes.  Through the pinned ring when
+// the image fits a segment: the device reads it there in place (in_ws false) or one async DMA moves it to the start of the
+// workspace (in_ws true: the caller has reserved it); the host buffers are free on return.  Pageable copies into the workspace
+// otherwise: *must_sync says that the caller has to synchronise before it returns (the sources may still be read, and the
+// workspace is the next call's).
+struct HostSpan {
+  const void* h;
+  size_t bytes, at;  // `bytes` from h belong `at` bytes into the image
+};
+static int stage_host(randt_ctx* ctx, const HostSpan* spans, int n_spans, size_t total, bool in_ws, const void** d, bool* must_sync) {
+  *must_sync = false;
+  if (char* pin = static_cast<char*>(randt_pin_take(ctx, total))) {
+    for (int i = 0; i < n_spans; ++i)
+      if (spans[i].bytes) memcpy(pin + spans[i].at, spans[i].h, spans[i].bytes);
+    *d = pin;
+    if (!in_ws) return RANDT_OK;
+    RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->ws.p, pin, total, hipMemcpyHostToDevice, ctx->stream));
+    *d = ctx->ws.p;
+    return RANDT_OK;
   }
-  *d_points = static_cast<const float*>(ctx->ws);
+  if (!in_ws) {
+    const int rc = randt_scratch_reserve(ctx, ctx->ws, total);
+    if (rc) return rc;
+  }
+  for (int i = 0; i < n_spans; ++i)
+    if (spans[i].bytes)
+      RANDT_HIP_CHECK(ctx, hipMemcpyAsync(static_cast<char*>(ctx->ws.p) + spans[i].at, spans[i].h, spans[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+  *d = ctx->ws.p;
+  *must_sync = true;
+  return RANDT_OK;
+}
+
+// host points -> the context's workspace: no synchronisation when they fit a segment of the pinned ring
+static int stage_points(randt_ctx* ctx, const float* h_points, size_t bytes, const float** d_points) {
+  int rc = randt_scratch_reserve(ctx, ctx->ws, bytes);
+  if (rc) return rc;
+  const HostSpan span{h_points, bytes, 0};
+  const void* d = nullptr;
+  bool must_sync = false;
+  rc = stage_host(ctx, &span, 1, bytes, true, &d, &must_sync);
+  if (rc) return rc;
+  if (must_sync) RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  *d_points = static_cast<const float*>(d);
   return RANDT_OK;
 }
 
@@ -857,7 +940,7 @@ int randt_ndt_build(randt_ctx* ctx, const float* h_points, int n_points, int str
   if (!ctx || n_points < 0 || (n_points > 0 && !h_points) || stride_floats < 3) return RANDT_ERR_INVALID;
   if (n_points == 0) return randt_maps_clear(out, map_idx, 1);
   const float* d_points = nullptr;
-  int rc = stage_points(ctx, h_points, sizeof(float) * (size_t)n_points * stride_floats, 0, &d_points);
+  int rc = stage_points(ctx, h_points, sizeof(float) * (size_t)n_points * stride_floats, &d_points);
   if (rc) return rc;
   return randt_ndt_build_batch_dev(ctx, d_points, 1, n_points, nullptr, stride_floats, intensity_index, cp, out, map_idx);
 }
@@ -868,22 +951,18 @@ int randt_ndt_build(randt_ctx* ctx, const float* h_points, int n_points, int str
 // launches and a synchronisation each), not the batched hot path.
 static int append_from(randt_maps* m, int idx, const randt_maps* src, int set_grid, int* n_dropped, int* n_outside) {
   randt_ctx* ctx = m->ctx;
-  char* d_blk = nullptr;
-  int rc = small_block(ctx, &d_blk);
+  SmallScratch* small = nullptr;
+  int rc = small_block(ctx, &small);
   if (rc) return rc;
-  int32_t* d_status = reinterpret_cast<int32_t*>(d_blk + 512);
+  int32_t* d_status = small->append.status;
   rc = launch_maps_append(ctx, m->v, idx, src->v, 0, set_grid, d_status, 0);
+  if (rc) return drained(ctx, rc);
   int32_t h_status[2] = {0, 0};
-  if (!rc) {
-    hipError_t e = hipMemcpyAsync(h_status, d_status, sizeof(h_status), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = randt_sync(ctx);
-    if (e != hipSuccess) rc = randt_set_error(ctx, RANDT_ERR_HIP, "append status read-back", e);
-  } else {
-    (void)randt_sync(ctx);
-  }
-  if (n_dropped) *n_dropped = h_status[0];
-  if (n_outside) *n_outside = h_status[1];
-  return rc;
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_status, d_status, sizeof(h_status), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  *n_dropped = h_status[0];
+  *n_outside = h_status[1];
+  return RANDT_OK;
 }
 
 // What asynchronous inserts (randt_maps_insert_cluster with accepted = NULL) could not report when they ran: the append
@@ -901,13 +980,13 @@ int randt_maps_insert_cells(randt_maps* m, int idx, const randt_cell* h_cells, i
   if (!range_ok(m, idx, 1) || n_cells < 0 || (n_cells > 0 && !h_cells)) return RANDT_ERR_INVALID;
   if (n_cells == 0) return RANDT_OK;
   randt_ctx* ctx = m->ctx;
-  randt_maps* tmp = nullptr;
-  int rc = maps_alloc(ctx, 1, &m->p, n_cells, 0, &tmp);  // pooled, fully overwritten by the upload
+  TmpMaps tmp;
+  int rc = maps_alloc(ctx, 1, &m->p, n_cells, 0, &tmp.m);  // pooled, fully overwritten by the upload
   if (rc) return rc;
-  rc = randt_maps_upload(tmp, 0, h_cells, n_cells, nullptr);
+  rc = randt_maps_upload(tmp.m, 0, h_cells, n_cells, nullptr);
+  if (rc) return rc;
   int dropped = 0, outside = 0;
-  if (!rc) rc = append_from(m, idx, tmp, set_grid, &dropped, &outside);
-  (void)randt_maps_destroy(tmp);
+  rc = append_from(m, idx, tmp.m, set_grid, &dropped, &outside);
   if (rc) return rc;
   if (outside) return randt_set_error(ctx, RANDT_ERR_INVALID, "cell mean outside the map's index grid", hipSuccess);
   if (dropped) return randt_set_error(ctx, RANDT_ERR_UNSUPPORTED, "map cell capacity exhausted", hipSuccess);
@@ -968,34 +1047,32 @@ int randt_maps_insert_clusters(randt_maps* m, int idx, const float* h_points, co
   const int n_points = h_offsets[n_clusters];
   if (n_points > 0 && !h_points) return RANDT_ERR_INVALID;
   randt_ctx* ctx = m->ctx;
-  // points | offsets | status (2) | accepted (1) in the workspace: through the pinned ring when they fit a segment
-  const size_t pb = (sizeof(float) * (size_t)n_points * stride_floats + 255) & ~(size_t)255, ob = (sizeof(int32_t) * ((size_t)n_clusters + 1) + 255) & ~(size_t)255;
-  int rc = ensure_ws(ctx, pb + ob + 256);
+  // points | offsets | status (2) + accepted (1) in the workspace
+  struct Layout { float* pts; int32_t *offsets, *tail; };
+  auto layout = [&](Carve& c) {
+    return Layout{c.take<float>((size_t)n_points * stride_floats), c.take<int32_t>((size_t)n_clusters + 1), c.take<int32_t>(3)};
+  };
+  int rc = randt_scratch_reserve(ctx, ctx->ws, carved_size(layout));
   if (rc) return rc;
-  char* ws = static_cast<char*>(ctx->ws);
-  bool waited = false;
-  if (char* pin = static_cast<char*>(randt_pin_take(ctx, pb + ob))) {
-    if (n_points) memcpy(pin, h_points, sizeof(float) * (size_t)n_points * stride_floats);
-    memcpy(pin + pb, h_offsets, sizeof(int32_t) * ((size_t)n_clusters + 1));
-    RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ws, pin, pb + ob, hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    if (n_points) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ws, h_points, sizeof(float) * (size_t)n_points * stride_floats, hipMemcpyHostToDevice, ctx->stream));
-    RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ws + pb, h_offsets, sizeof(int32_t) * ((size_t)n_clusters + 1), hipMemcpyHostToDevice, ctx->stream));
-    RANDT_HIP_CHECK(ctx, randt_sync(ctx));  // pageable sources
-    waited = true;
-  }
-  (void)waited;
-  int32_t* d_tail = reinterpret_cast<int32_t*>(ws + pb + ob);
+  Carve c(ctx->ws.p);
+  const Layout L = layout(c);
+  const size_t ob = sizeof(int32_t) * ((size_t)n_clusters + 1), off_offsets = (size_t)((char*)L.offsets - (char*)L.pts);
+  const HostSpan spans[2] = {{h_points, sizeof(float) * (size_t)n_points * stride_floats, 0}, {h_offsets, ob, off_offsets}};
+  const void* d = nullptr;
+  bool must_sync = false;
+  rc = stage_host(ctx, spans, 2, off_offsets + ob, true, &d, &must_sync);
+  if (rc) return rc;
+  if (must_sync) RANDT_HIP_CHECK(ctx, randt_sync(ctx));  // pageable sources
   const bool deferred = !n_accepted && m->owns;  // nothing comes back: the unplaceable clusters are reported by the next synchronising read
-  rc = launch_maps_insert_clusters(ctx, m->v, idx, reinterpret_cast<const float*>(ws), reinterpret_cast<const int32_t*>(ws + pb), n_clusters, stride_floats,
-                                   intensity_index, deferred ? m->v.counts + m->v.n_maps : d_tail, deferred ? 1 : 0, d_tail + 2);
+  rc = launch_maps_insert_clusters(ctx, m->v, idx, L.pts, L.offsets, n_clusters, stride_floats, intensity_index,
+                                   deferred ? m->v.counts + m->v.n_maps : L.tail, deferred ? 1 : 0, L.tail + 2);
   if (rc) return rc;
   if (deferred) {
     m->deferred_pending = true;
     return RANDT_OK;
   }
   int32_t h_tail[3] = {0, 0, 0};
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_tail, d_tail, sizeof(h_tail), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_tail, L.tail, sizeof(h_tail), hipMemcpyDeviceToHost, ctx->stream));
   RANDT_HIP_CHECK(ctx, randt_sync(ctx));
   if (n_accepted) *n_accepted = h_tail[2];
   if (h_tail[1]) return randt_set_error(ctx, RANDT_ERR_INVALID, "cluster mean outside the map's index grid", hipSuccess);
@@ -1010,56 +1087,50 @@ int randt_closest_cells(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, 
   if (n_queries == 0) return RANDT_OK;
   if (!h_queries || !h_out) return RANDT_ERR_INVALID;
   randt_note_user(ctx, fixed);
-  randt_maps* tmp = nullptr;
-  int rc = maps_alloc(ctx, 1, &fixed->p, n_queries, 0, &tmp);  // pooled, fully overwritten by the upload
+  TmpMaps tmp;
+  int rc = maps_alloc(ctx, 1, &fixed->p, n_queries, 0, &tmp.m);  // pooled, fully overwritten by the upload
   if (rc) return rc;
-  rc = randt_maps_upload(tmp, 0, h_queries, n_queries, nullptr);
-  char* d_blk = nullptr;
-  size_t blk_bytes = 0;
-  const size_t corr_bytes = sizeof(int32_t) * (size_t)n_queries * k;
-  if (!rc && randt_dev_alloc(ctx, reinterpret_cast<void**>(&d_blk), 256 + corr_bytes, &blk_bytes) != hipSuccess) {
+  rc = randt_maps_upload(tmp.m, 0, h_queries, n_queries, nullptr);
+  if (rc) return rc;
+  // identity pose | fixed index | correspondence rows in a pooled block
+  struct Layout { double* pose; int32_t *fixed_idx, *corr; };
+  auto layout = [&](Carve& c) { return Layout{c.take<double>(4), c.take<int32_t>(1, 64), c.take<int32_t>((size_t)n_queries * k)}; };
+  PooledBlock blk(ctx);
+  if (blk.alloc(carved_size(layout)) != hipSuccess) {
     (void)hipGetLastError();
-    d_blk = nullptr;
-    rc = randt_set_error(ctx, RANDT_ERR_NOMEM, "hipMalloc", hipErrorOutOfMemory);
+    blk.p = nullptr;
+    return randt_set_error(ctx, RANDT_ERR_NOMEM, "hipMalloc", hipErrorOutOfMemory);
   }
-  if (!rc) {
-    const double ident[4] = {1.0, 0.0, 0.0, 0.0};
-    double* d_pose = reinterpret_cast<double*>(d_blk);
-    int32_t* d_fi = reinterpret_cast<int32_t*>(d_blk + 64);
-    int32_t* d_corr = reinterpret_cast<int32_t*>(d_blk + 256);
-    hipError_t e = hipMemcpyAsync(d_pose, ident, sizeof(ident), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_fi, &fixed_idx, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) rc = randt_set_error(ctx, RANDT_ERR_HIP, "hipMemcpyAsync", e);
-    if (!rc) rc = launch_associate(ctx, fixed->v, d_fi, tmp->v, 0, 1, d_pose, k, lookup_mahalanobis, use_intensity, d_corr);
-    if (!rc) {
-      e = hipMemcpyAsync(h_out, d_corr, corr_bytes, hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) e = randt_sync(ctx);
-      if (e != hipSuccess) rc = randt_set_error(ctx, RANDT_ERR_HIP, "closest cells read-back", e);
-    } else {
-      (void)randt_sync(ctx);
-    }
-  }
-  if (d_blk) randt_dev_release(ctx, d_blk, blk_bytes);
-  (void)randt_maps_destroy(tmp);
-  return rc;
+  Carve c(blk.p);
+  const Layout L = layout(c);
+  const double ident[4] = {1.0, 0.0, 0.0, 0.0};
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.pose, ident, sizeof(ident), hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.fixed_idx, &fixed_idx, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  rc = launch_associate(ctx, fixed->v, L.fixed_idx, tmp.m->v, 0, 1, L.pose, k, lookup_mahalanobis, use_intensity, L.corr);
+  if (rc) return drained(ctx, rc);
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_out, L.corr, sizeof(int32_t) * (size_t)n_queries * k, hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  return RANDT_OK;
 }
 
 // ---------------------------------------------------------------- single cells (facade Cell mutators) ---------
 namespace {
 // stage n cells (and optionally n more) in the workspace, run one cell kernel, read back what it produced
 int cells_roundtrip(randt_ctx* ctx, int op, randt_cell* h_a, const randt_cell* h_b, int n, const double* h_pose4, double* h_out) {
+  struct Layout { randt_cell *a, *b; double *pose, *out; };
+  auto layout = [&](Carve& c) { return Layout{c.take<randt_cell>(n), c.take<randt_cell>(n), c.take<double>(4), c.take<double>(n)}; };
+  int rc = randt_scratch_reserve(ctx, ctx->ws, carved_size(layout));
+  if (rc) return rc;
+  Carve c(ctx->ws.p);
+  const Layout L = layout(c);
   const size_t cb = sizeof(randt_cell) * (size_t)n;
-  const size_t off_b = (cb + 255) & ~(size_t)255, off_pose = off_b + ((cb + 255) & ~(size_t)255), off_out = off_pose + 256;
-  int rc = ensure_ws(ctx, off_out + sizeof(double) * (size_t)n + 256);
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.a, h_a, cb, hipMemcpyHostToDevice, ctx->stream));
+  if (h_b) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.b, h_b, cb, hipMemcpyHostToDevice, ctx->stream));
+  if (h_pose4) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.pose, h_pose4, sizeof(double) * 4, hipMemcpyHostToDevice, ctx->stream));
+  rc = launch_cells_op(ctx, op, L.a, L.b, n, L.pose, L.out);
   if (rc) return rc;
-  char* ws = (char*)ctx->ws;
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ws, h_a, cb, hipMemcpyHostToDevice, ctx->stream));
-  if (h_b) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ws + off_b, h_b, cb, hipMemcpyHostToDevice, ctx->stream));
-  if (h_pose4) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ws + off_pose, h_pose4, sizeof(double) * 4, hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_cells_op(ctx, op, (randt_cell*)ws, (const randt_cell*)(ws + off_b), n, (const double*)(ws + off_pose), (double*)(ws + off_out));
-  if (rc) return rc;
-  if (h_out) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_out, ws + off_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  else RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_a, ws, cb, hipMemcpyDeviceToHost, ctx->stream));
+  if (h_out) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_out, L.out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  else RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_a, L.a, cb, hipMemcpyDeviceToHost, ctx->stream));
   RANDT_HIP_CHECK(ctx, randt_sync(ctx));
   return RANDT_OK;
 }
@@ -1083,15 +1154,18 @@ int randt_points_transform(randt_ctx* ctx, float* h_points, int n_points, int st
   DeviceGuard dev_guard__(ctx);
   if (!ctx || n_points < 0 || stride_floats < 3 || !h_pose4 || (n_points > 0 && !h_points)) return RANDT_ERR_INVALID;
   if (n_points == 0) return RANDT_OK;
-  const size_t pb = sizeof(float) * (size_t)n_points * stride_floats, off_pose = (pb + 255) & ~(size_t)255;
-  int rc = ensure_ws(ctx, off_pose + 64);
+  struct Layout { float* pts; double* pose; };
+  auto layout = [&](Carve& c) { return Layout{c.take<float>((size_t)n_points * stride_floats), c.take<double>(4)}; };
+  int rc = randt_scratch_reserve(ctx, ctx->ws, carved_size(layout));
   if (rc) return rc;
-  char* ws = (char*)ctx->ws;
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ws, h_points, pb, hipMemcpyHostToDevice, ctx->stream));
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ws + off_pose, h_pose4, sizeof(double) * 4, hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_points_transform(ctx, (float*)ws, n_points, stride_floats, (const double*)(ws + off_pose));
+  Carve c(ctx->ws.p);
+  const Layout L = layout(c);
+  const size_t pb = sizeof(float) * (size_t)n_points * stride_floats;
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.pts, h_points, pb, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.pose, h_pose4, sizeof(double) * 4, hipMemcpyHostToDevice, ctx->stream));
+  rc = launch_points_transform(ctx, L.pts, n_points, stride_floats, L.pose);
   if (rc) return rc;
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_points, ws, pb, hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_points, L.pts, pb, hipMemcpyDeviceToHost, ctx->stream));
   RANDT_HIP_CHECK(ctx, randt_sync(ctx));
   return RANDT_OK;
 }
@@ -1112,19 +1186,19 @@ int randt_cell_add_points(randt_ctx* ctx, randt_cell* h_cell, const float* h_poi
     return RANDT_ERR_INVALID;
   if (accepted) *accepted = 0;
   if (n_points == 0) return RANDT_OK;
-  const size_t pb = sizeof(float) * (size_t)n_points * stride_floats;
-  const size_t off_cell = (pb + 255) & ~(size_t)255, off_acc = off_cell + 256;
-  int rc = ensure_ws(ctx, off_acc + 64);
+  struct Layout { float* pts; randt_cell* cell; int32_t* accepted; };
+  auto layout = [&](Carve& c) { return Layout{c.take<float>((size_t)n_points * stride_floats), c.take<randt_cell>(1), c.take<int32_t>(1)}; };
+  int rc = randt_scratch_reserve(ctx, ctx->ws, carved_size(layout));
   if (rc) return rc;
-  char* ws = (char*)ctx->ws;
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ws, h_points, pb, hipMemcpyHostToDevice, ctx->stream));
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ws + off_cell, h_cell, sizeof(randt_cell), hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_cell_update(ctx, (randt_cell*)(ws + off_cell), (const float*)ws, n_points, stride_floats, intensity_index, min_points_per_cell,
-                          (int32_t*)(ws + off_acc));
+  Carve c(ctx->ws.p);
+  const Layout L = layout(c);
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.pts, h_points, sizeof(float) * (size_t)n_points * stride_floats, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.cell, h_cell, sizeof(randt_cell), hipMemcpyHostToDevice, ctx->stream));
+  rc = launch_cell_update(ctx, L.cell, L.pts, n_points, stride_floats, intensity_index, min_points_per_cell, L.accepted);
   if (rc) return rc;
   int32_t acc = 0;
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_cell, ws + off_cell, sizeof(randt_cell), hipMemcpyDeviceToHost, ctx->stream));
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(&acc, ws + off_acc, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_cell, L.cell, sizeof(randt_cell), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(&acc, L.accepted, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));
   RANDT_HIP_CHECK(ctx, randt_sync(ctx));
   if (accepted) *accepted = acc;
   return RANDT_OK;
@@ -1138,21 +1212,18 @@ int randt_maps_reindex(randt_maps* m, int first, int count) {
 }
 
 // host poses for a kernel of this stream: the pinned ring (read by the device in place, nothing to wait for), else the
-// workspace + a synchronisation
+// workspace + a synchronisation behind the kernel
 static int stage_poses(randt_ctx* ctx, const double* h_pose4, int count, const double** d_pose4, bool* must_sync) {
-  const size_t bytes = sizeof(double) * 4 * (size_t)count;
-  *must_sync = false;
-  if (void* pin = randt_pin_take(ctx, bytes)) {
-    memcpy(pin, h_pose4, bytes);
-    *d_pose4 = static_cast<const double*>(pin);
-    return RANDT_OK;
-  }
-  int rc = ensure_ws(ctx, bytes);
-  if (rc) return rc;
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->ws, h_pose4, bytes, hipMemcpyHostToDevice, ctx->stream));
-  *d_pose4 = static_cast<const double*>(ctx->ws);
-  *must_sync = true;  // ws is reused by the next call
-  return RANDT_OK;
+  const HostSpan span{h_pose4, sizeof(double) * 4 * (size_t)count, 0};
+  const void* d = nullptr;
+  const int rc = stage_host(ctx, &span, 1, span.bytes, false, &d, must_sync);
+  *d_pose4 = static_cast<const double*>(d);
+  return rc;
+}
+// ... and the tail of the entries that launch one kernel on them
+static int staged_tail(randt_ctx* ctx, int launch_rc, bool must_sync) {
+  if (launch_rc) return launch_rc;
+  return must_sync ? randt_ctx_synchronize(ctx) : RANDT_OK;
 }
 
 int randt_maps_transform(randt_maps* m, int first, int count, const double* h_pose4) {
@@ -1164,9 +1235,7 @@ int randt_maps_transform(randt_maps* m, int first, int count, const double* h_po
   bool must_sync = false;
   int rc = stage_poses(ctx, h_pose4, count, &d_pose4, &must_sync);
   if (rc) return rc;
-  rc = launch_maps_transform(ctx, m->v, first, count, d_pose4);
-  if (rc) return rc;
-  return must_sync ? randt_ctx_synchronize(ctx) : RANDT_OK;
+  return staged_tail(ctx, launch_maps_transform(ctx, m->v, first, count, d_pose4), must_sync);
 }
 
 int randt_maps_merge(randt_maps* fixed, int fixed_idx, const randt_maps* moving, int moving_first, int n_moving,
@@ -1183,9 +1252,7 @@ int randt_maps_merge(randt_maps* fixed, int fixed_idx, const randt_maps* moving,
   bool must_sync = false;
   int rc = stage_poses(ctx, h_pose4, n_moving, &d_pose4, &must_sync);
   if (rc) return rc;
-  rc = launch_maps_merge(ctx, fixed->v, fixed_idx, moving->v, moving_first, n_moving, d_pose4);
-  if (rc) return rc;
-  return must_sync ? randt_ctx_synchronize(ctx) : RANDT_OK;
+  return staged_tail(ctx, launch_maps_merge(ctx, fixed->v, fixed_idx, moving->v, moving_first, n_moving, d_pose4), must_sync);
 }
 
 int randt_maps_merge_batch(randt_maps* fixed, int fixed_first, int n_fixed, const randt_maps* moving, int moving_first, int n_moving_each,
@@ -1203,9 +1270,7 @@ int randt_maps_merge_batch(randt_maps* fixed, int fixed_first, int n_fixed, cons
   bool must_sync = false;
   int rc = stage_poses(ctx, h_pose4, n_fixed * n_moving_each, &d_pose4, &must_sync);
   if (rc) return rc;
-  rc = launch_maps_merge(ctx, fixed->v, fixed_first, moving->v, moving_first, n_moving_each, d_pose4, n_fixed);
-  if (rc) return rc;
-  return must_sync ? randt_ctx_synchronize(ctx) : RANDT_OK;
+  return staged_tail(ctx, launch_maps_merge(ctx, fixed->v, fixed_first, moving->v, moving_first, n_moving_each, d_pose4, n_fixed), must_sync);
 }
 
 // The solve kernels run the reference's GNC / trust-region loops ON THE DEVICE (`do { ... mu /= divisor } while (mu > 1 /
@@ -1286,9 +1351,9 @@ int randt_register_batch_dev(randt_ctx* ctx, const randt_maps* fixed, const int3
   randt_note_user(ctx, fixed);
   randt_note_user(ctx, moving);
   size_t corr_bytes = sizeof(int32_t) * (size_t)n_pairs * moving->v.cap * mp->n_neighbours;
-  rc = ensure_ws(ctx, corr_bytes);
+  rc = randt_scratch_reserve(ctx, ctx->ws, corr_bytes);
   if (rc) return rc;
-  int32_t* d_corr = (int32_t*)ctx->ws;
+  int32_t* d_corr = static_cast<int32_t*>(ctx->ws.p);
   rc = launch_associate(ctx, fixed->v, d_fixed_idx, moving->v, moving_first, n_pairs, d_pose4, mp->n_neighbours,
                         mp->lookup_mahalanobis, mp->use_intensity, d_corr);
   if (rc) return rc;
@@ -1311,34 +1376,22 @@ int randt_register_pair(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, 
                         const randt_matcher_params* mp, double h_pose4[4], randt_result* h_result) {
   DeviceGuard dev_guard__(ctx);
   if (!ctx || !h_pose4 || !range_ok(fixed, fixed_idx, 1) || !range_ok(moving, moving_idx, 1) || !mp) return RANDT_ERR_INVALID;
-  // small staging block: [pose4 | result | fixed_idx]
-  char* stage = nullptr;
-  int rc0 = small_block(ctx, &stage);
-  if (rc0) return rc0;
-  stage += 1024;  // own region of the context's scratch block
-  double* d_pose = (double*)stage;
-  randt_result* d_res = (randt_result*)(d_pose + 4);
-  int32_t* d_fi = (int32_t*)(d_res + 1);
-  int32_t fi = fixed_idx;
-  hipError_t e1 = hipMemcpyAsync(d_pose, h_pose4, sizeof(double) * 4, hipMemcpyHostToDevice, ctx->stream);
-  hipError_t e2 = hipMemcpyAsync(d_fi, &fi, sizeof(fi), hipMemcpyHostToDevice, ctx->stream);
-  int rc = (e1 != hipSuccess || e2 != hipSuccess) ? randt_set_error(ctx, RANDT_ERR_HIP, "hipMemcpyAsync", e1 != hipSuccess ? e1 : e2) : RANDT_OK;
-  if (!rc) rc = randt_register_batch_dev(ctx, fixed, d_fi, moving, moving_idx, 1, mp, d_pose, d_res);
+  if (h_result) memset(h_result, 0, sizeof(*h_result));
+  SmallScratch* small = nullptr;
+  int rc = small_block(ctx, &small);
+  if (rc) return rc;
+  auto& d = small->pair;
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(d.pose, h_pose4, sizeof(double) * 4, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(&d.fixed_idx, &fixed_idx, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  rc = randt_register_batch_dev(ctx, fixed, &d.fixed_idx, moving, moving_idx, 1, mp, d.pose, &d.res);
+  if (rc) return drained(ctx, rc);
   randt_result r;
-  memset(&r, 0, sizeof(r));
-  if (!rc) {
-    hipError_t e3 = hipMemcpyAsync(h_pose4, d_pose, sizeof(double) * 4, hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t e4 = hipMemcpyAsync(&r, d_res, sizeof(r), hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t e5 = randt_sync(ctx);
-    if (e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess)
-      rc = randt_set_error(ctx, RANDT_ERR_HIP, "download", e5 != hipSuccess ? e5 : (e3 != hipSuccess ? e3 : e4));
-  } else {
-    (void)randt_sync(ctx);
-  }
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_pose4, d.pose, sizeof(double) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(&r, &d.res, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
   if (h_result) *h_result = r;
-  return rc;
+  return RANDT_OK;
 }
-
 
 int randt_eval_cost_batch_dev(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, const randt_maps* moving, int moving_idx,
                               const int32_t* d_corr, const randt_matcher_params* mp, double scale, const double* d_poses4,
@@ -1365,38 +1418,28 @@ int randt_cs_divergence_batch_dev(randt_ctx* ctx, const randt_maps* fixed, int f
   randt_note_user(ctx, fixed);
   randt_note_user(ctx, moving);
   const int max_tiles = (fixed->v.cap + RANDT_CS_SELF_OUTER - 1) / RANDT_CS_SELF_OUTER;  // partial sums of the fixed maps' self terms (csdiv.hip)
-  int rc = ensure_ws(ctx, sizeof(double) * (size_t)fixed_count * max_tiles + 256);
+  int rc = randt_scratch_reserve(ctx, ctx->ws, sizeof(double) * (size_t)fixed_count * max_tiles + 256);
   if (rc) return rc;
   return launch_cs_divergence(ctx, fixed->v, fixed_first, fixed_count, d_fixed_idx, moving->v, moving_first, n_pairs, d_pose4,
-                              (double*)ctx->ws, d_out, d_terms);
+                              static_cast<double*>(ctx->ws.p), d_out, d_terms);
 }
 
 int randt_cs_divergence(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, const randt_maps* moving, int moving_idx,
                         const double* h_pose4, double* out, double* h_terms) {
   DeviceGuard dev_guard__(ctx);
   if (!ctx || !out || !range_ok(fixed, fixed_idx, 1) || !range_ok(moving, moving_idx, 1)) return RANDT_ERR_INVALID;
-  // device scratch of this call: pose | fixed index | result | terms (kept apart from the workspace the batch entry uses)
-  char* d_blk = nullptr;
-  int rc = small_block(ctx, &d_blk);
+  SmallScratch* small = nullptr;
+  int rc = small_block(ctx, &small);
   if (rc) return rc;
-  double* d_pose = reinterpret_cast<double*>(d_blk);
-  int32_t* d_fi = reinterpret_cast<int32_t*>(d_blk + 64);
-  double* d_out = reinterpret_cast<double*>(d_blk + 128);
-  double* d_terms = d_out + 1;
-  hipError_t e = hipSuccess;
-  if (h_pose4) e = hipMemcpyAsync(d_pose, h_pose4, sizeof(double) * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_fi, &fixed_idx, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) rc = randt_set_error(ctx, RANDT_ERR_HIP, "hipMemcpyAsync", e);
-  if (!rc) rc = randt_cs_divergence_batch_dev(ctx, fixed, fixed_idx, 1, d_fi, moving, moving_idx, 1, h_pose4 ? d_pose : nullptr, d_out, d_terms);
-  if (!rc) {
-    e = hipMemcpyAsync(out, d_out, sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && h_terms) e = hipMemcpyAsync(h_terms, d_terms, sizeof(double) * 3, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = randt_sync(ctx);
-    if (e != hipSuccess) rc = randt_set_error(ctx, RANDT_ERR_HIP, "cs divergence read-back", e);
-  } else {
-    (void)randt_sync(ctx);
-  }
-  return rc;
+  auto& d = small->cs;
+  if (h_pose4) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(d.pose, h_pose4, sizeof(double) * 4, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(&d.fixed_idx, &fixed_idx, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  rc = randt_cs_divergence_batch_dev(ctx, fixed, fixed_idx, 1, &d.fixed_idx, moving, moving_idx, 1, h_pose4 ? d.pose : nullptr, &d.out, d.terms);
+  if (rc) return drained(ctx, rc);
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(out, &d.out, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (h_terms) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_terms, d.terms, sizeof(double) * 3, hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  return RANDT_OK;
 }
 
 int randt_sc_make_batch_dev(randt_ctx* ctx, const float* d_points, int n_scans, int points_pitch, const int32_t* d_n_points,
@@ -1418,9 +1461,9 @@ int randt_sc_detect_batch_dev(randt_ctx* ctx, const randt_sc_params* p, const do
   if (!ctx || !p || n_db < 0 || n_queries < 0) return RANDT_ERR_INVALID;
   if (n_queries == 0) return RANDT_OK;
   if (!d_desc || !d_ring_keys || !d_pos || !d_dist || !d_loop_id || !d_yaw) return RANDT_ERR_INVALID;
-  int rc = ensure_ws(ctx, sc_detect_ws_bytes(n_queries, n_db, p->num_candidates));
+  int rc = randt_scratch_reserve(ctx, ctx->ws, sc_detect_ws_bytes(n_queries, n_db, p->num_candidates));
   if (rc) return rc;
-  return launch_sc_detect(ctx, p, d_desc, d_ring_keys, d_pos, d_dist, n_db, d_query_ids, n_queries, (float*)ctx->ws, d_loop_id, d_yaw,
+  return launch_sc_detect(ctx, p, d_desc, d_ring_keys, d_pos, d_dist, n_db, d_query_ids, n_queries, static_cast<float*>(ctx->ws.p), d_loop_id, d_yaw,
                           d_min_dist);
 }
 
@@ -1501,14 +1544,16 @@ int randt_sc_db_append(randt_sc_db* db, const float* h_points, int n_points, int
   int rc = sc_db_reserve(db, db->n + 1);
   if (rc) return rc;
   const int pitch = n_points > 0 ? n_points : 1;
-  const size_t bytes = sizeof(float) * (size_t)pitch * stride_floats;
-  rc = ensure_ws(ctx, bytes + 64);
+  struct Layout { float* pts; int32_t* n; };
+  auto layout = [&](Carve& c) { return Layout{c.take<float>((size_t)pitch * stride_floats), c.take<int32_t>(1, 16)}; };
+  rc = randt_scratch_reserve(ctx, ctx->ws, carved_size(layout));
   if (rc) return rc;
-  if (n_points > 0) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->ws, h_points, bytes, hipMemcpyHostToDevice, ctx->stream));
-  int32_t* d_n = reinterpret_cast<int32_t*>((char*)ctx->ws + ((bytes + 15) & ~(size_t)15));
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(d_n, &n_points, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  Carve c(ctx->ws.p);
+  const Layout L = layout(c);
+  if (n_points > 0) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.pts, h_points, sizeof(float) * (size_t)pitch * stride_floats, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.n, &n_points, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   const size_t nd = (size_t)db->p.num_ring * db->p.num_sector;
-  rc = launch_sc_make(ctx, (const float*)ctx->ws, 1, pitch, d_n, stride_floats, intensity_index, &db->p, db->desc + nd * db->n,
+  rc = launch_sc_make(ctx, L.pts, 1, pitch, L.n, stride_floats, intensity_index, &db->p, db->desc + nd * db->n,
                       db->ring + (size_t)db->p.num_ring * db->n, db->sector + (size_t)db->p.num_sector * db->n);
   if (rc) return rc;
   const double pd[3] = {odom_position[0], odom_position[1], traversed_distance};
@@ -1524,11 +1569,11 @@ int randt_sc_db_detect(randt_sc_db* db, int node_id, int* loop_id, float* yaw_di
   DeviceGuard dev_guard__(db ? db->ctx : nullptr);
   if (!db || !loop_id || !yaw_diff_rad || node_id < 0 || node_id >= db->n) return RANDT_ERR_INVALID;
   randt_ctx* ctx = db->ctx;
-  int rc = ensure_ws(ctx, sc_detect_ws_bytes(1, db->n, db->p.num_candidates));
+  int rc = randt_scratch_reserve(ctx, ctx->ws, sc_detect_ws_bytes(1, db->n, db->p.num_candidates));
   if (rc) return rc;
   int32_t* d_q = db->out_id + 1;
   RANDT_HIP_CHECK(ctx, hipMemcpyAsync(d_q, &node_id, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_sc_detect(ctx, &db->p, db->desc, db->ring, db->pos, db->dist, db->n, d_q, 1, (float*)ctx->ws, db->out_id, db->out_yaw,
+  rc = launch_sc_detect(ctx, &db->p, db->desc, db->ring, db->pos, db->dist, db->n, d_q, 1, static_cast<float*>(ctx->ws.p), db->out_id, db->out_yaw,
                         db->out_md);
   if (rc) return rc;
   int32_t id = -1;
@@ -1570,43 +1615,38 @@ int randt_filter_scan_batch_dev(randt_ctx* ctx, const float* d_raw, int n_scans,
   if (!d_raw || !d_out_points || !d_out_counts || !d_status) return RANDT_ERR_INVALID;
   if (stride_floats == 4 && ((size_t)d_raw & 15) != 0) return randt_set_error(ctx, RANDT_ERR_INVALID, "packed xyzI input must be 16-byte aligned", hipSuccess);
   if ((long long)n_azimuths * n_bins > (1ll << 30)) return RANDT_ERR_UNSUPPORTED;
-  int rc = ensure_ws(ctx, (size_t)n_scans * n_azimuths * (32 + 4 * 2 * 16) + 512);  // row records + FILT_STAGE staged points per row (filter.hip)
+  int rc = randt_scratch_reserve(ctx, ctx->ws, (size_t)n_scans * n_azimuths * (32 + 4 * 2 * 16) + 512);  // row records + FILT_STAGE staged points per row (filter.hip)
   if (rc) return rc;
   return launch_filter_scan(ctx, d_raw, n_scans, n_azimuths, n_bins, stride_floats, intensity_index, fp, d_out_points, pitch_out,
-                            d_out_counts, d_out_polar, d_peaks, d_peak_counts, d_status, ctx->ws);
+                            d_out_counts, d_out_polar, d_peaks, d_peak_counts, d_status, ctx->ws.p);
 }
 
-// one raw scan from the host into a pooled device block [raw | points | polar | peaks | counts, peak count, status]
+// one raw scan from the host into a pooled device block [raw | points | polar | peaks | count, peak count, status]
 namespace {
 struct FilterBlock {
-  char* base = nullptr;
-  size_t bytes = 0;
+  PooledBlock blk;
   float *raw = nullptr, *pts = nullptr, *polar = nullptr, *peaks = nullptr;
   int32_t* tail = nullptr;  // [0] count, [1] peak count, [2] status
+  explicit FilterBlock(randt_ctx* ctx) : blk(ctx) {}
+  void carve(Carve& c, int n_az, int n_bins, int stride, int capacity, bool want_polar, bool want_peaks) {
+    raw = c.take<float>((size_t)n_az * n_bins * stride);
+    pts = c.take<float>(4 * (size_t)capacity);
+    polar = want_polar ? c.take<float>(2 * (size_t)capacity) : nullptr;
+    peaks = want_peaks ? c.take<float>(3 * (size_t)n_az) : nullptr;
+    tail = c.take<int32_t>(3);
+  }
 };
 int filter_upload(randt_ctx* ctx, const float* h_raw, int n_az, int n_bins, int stride, int capacity, bool want_polar, bool want_peaks, FilterBlock* b) {
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t rb = up(sizeof(float) * (size_t)n_az * n_bins * stride), pb = up(sizeof(float) * 4 * (size_t)capacity),
-               qb = want_polar ? up(sizeof(float) * 2 * (size_t)capacity) : 0, kb = want_peaks ? up(sizeof(float) * 3 * (size_t)n_az) : 0;
-  void* blk = nullptr;
-  hipError_t e = randt_dev_alloc(ctx, &blk, rb + pb + qb + kb + 256, &b->bytes);
+  const hipError_t e = b->blk.alloc(carved_size([&](Carve& c) { b->carve(c, n_az, n_bins, stride, capacity, want_polar, want_peaks); }));
   if (e != hipSuccess) {
     (void)hipGetLastError();
+    b->blk.p = nullptr;
     return randt_set_error(ctx, e == hipErrorOutOfMemory ? RANDT_ERR_NOMEM : RANDT_ERR_HIP, "hipMalloc (raw scan)", e);
   }
-  b->base = static_cast<char*>(blk);
-  b->raw = reinterpret_cast<float*>(b->base);
-  b->pts = reinterpret_cast<float*>(b->base + rb);
-  b->polar = want_polar ? reinterpret_cast<float*>(b->base + rb + pb) : nullptr;
-  b->peaks = want_peaks ? reinterpret_cast<float*>(b->base + rb + pb + qb) : nullptr;
-  b->tail = reinterpret_cast<int32_t*>(b->base + rb + pb + qb + kb);
-  e = hipMemcpyAsync(b->raw, h_raw, sizeof(float) * (size_t)n_az * n_bins * stride, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = randt_sync(ctx);  // the caller's buffer (pageable or pinned) is free on return
-  if (e != hipSuccess) {
-    randt_dev_release(ctx, blk, b->bytes);
-    b->base = nullptr;
-    return randt_set_error(ctx, RANDT_ERR_HIP, "raw scan upload", e);
-  }
+  Carve c(b->blk.p);
+  b->carve(c, n_az, n_bins, stride, capacity, want_polar, want_peaks);
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(b->raw, h_raw, sizeof(float) * (size_t)n_az * n_bins * stride, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));  // the caller's buffer (pageable or pinned) is free on return
   return RANDT_OK;
 }
 }  // namespace
@@ -1618,26 +1658,20 @@ int randt_filter_scan(randt_ctx* ctx, const float* h_raw, int n_azimuths, int n_
   if (!ctx || !fp || !h_raw || !h_out_points || !n_out || !status || n_azimuths <= 0 || n_bins <= 0 || capacity <= 0 || stride_floats < 3 ||
       intensity_index < 0 || intensity_index >= stride_floats || (long long)n_azimuths * n_bins > (1ll << 30))
     return RANDT_ERR_INVALID;
-  FilterBlock b;
+  FilterBlock b(ctx);
   int rc = filter_upload(ctx, h_raw, n_azimuths, n_bins, stride_floats, capacity, h_out_polar != nullptr, h_peaks != nullptr, &b);
   if (rc) return rc;
   rc = randt_filter_scan_batch_dev(ctx, b.raw, 1, n_azimuths, n_bins, stride_floats, intensity_index, fp, b.pts, capacity, b.tail, b.polar, b.peaks,
                                    h_peaks ? b.tail + 1 : nullptr, b.tail + 2);
+  if (rc) return drained(ctx, rc);
   int32_t h_tail[3] = {0, 0, 0};
-  if (!rc) {
-    hipError_t e = hipMemcpyAsync(h_tail, b.tail, sizeof(h_tail), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = randt_sync(ctx);
-    const int n = h_tail[0] < capacity ? h_tail[0] : capacity;
-    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(h_out_points, b.pts, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && n > 0 && h_out_polar) e = hipMemcpyAsync(h_out_polar, b.polar, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && h_peaks && h_tail[1] > 0) e = hipMemcpyAsync(h_peaks, b.peaks, sizeof(float) * 3 * (size_t)h_tail[1], hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = randt_sync(ctx);
-    if (e != hipSuccess) rc = randt_set_error(ctx, RANDT_ERR_HIP, "filter read-back", e);
-  } else {
-    (void)randt_sync(ctx);
-  }
-  randt_dev_release(ctx, b.base, b.bytes);
-  if (rc) return rc;
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_tail, b.tail, sizeof(h_tail), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  const int n = h_tail[0] < capacity ? h_tail[0] : capacity;
+  if (n > 0) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_out_points, b.pts, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (n > 0 && h_out_polar) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_out_polar, b.polar, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (h_peaks && h_tail[1] > 0) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_peaks, b.peaks, sizeof(float) * 3 * (size_t)h_tail[1], hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
   *n_out = h_tail[0];
   if (n_peaks) *n_peaks = h_tail[1];
   *status = h_tail[2];
@@ -1650,21 +1684,19 @@ int randt_filter_build(randt_ctx* ctx, const float* h_raw, int n_azimuths, int n
   if (!ctx || !fp || !cp || !h_raw || !range_ok(out, map_idx, 1) || n_azimuths <= 0 || n_bins <= 0 || max_points <= 0 || stride_floats < 3 ||
       intensity_index < 0 || intensity_index >= stride_floats || (long long)n_azimuths * n_bins > (1ll << 30))
     return RANDT_ERR_INVALID;
-  FilterBlock b;
+  FilterBlock b(ctx);  // parked again at scope exit: whatever reuses it is enqueued behind the two kernels
   int rc = filter_upload(ctx, h_raw, n_azimuths, n_bins, stride_floats, max_points, false, false, &b);
   if (rc) return rc;
   rc = randt_filter_scan_batch_dev(ctx, b.raw, 1, n_azimuths, n_bins, stride_floats, intensity_index, fp, b.pts, max_points, b.tail, nullptr, nullptr,
                                    nullptr, b.tail + 2);
-  if (!rc) rc = randt_ndt_build_batch_dev(ctx, b.pts, 1, max_points, b.tail, 4, 3, cp, out, map_idx);
+  if (rc) return rc;
+  rc = randt_ndt_build_batch_dev(ctx, b.pts, 1, max_points, b.tail, 4, 3, cp, out, map_idx);
+  if (rc || !status) return rc;
   int32_t h_status = 0;
-  if (!rc && status) {
-    hipError_t e = hipMemcpyAsync(&h_status, b.tail + 2, sizeof(h_status), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = randt_sync(ctx);
-    if (e != hipSuccess) rc = randt_set_error(ctx, RANDT_ERR_HIP, "filter status read-back", e);
-  }
-  randt_dev_release(ctx, b.base, b.bytes);  // parked: whatever reuses it is enqueued behind the two kernels
-  if (!rc && status) *status = h_status;
-  return rc;
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(&h_status, b.tail + 2, sizeof(h_status), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  *status = h_status;
+  return RANDT_OK;
 }
 
 // ------------------------------------------------------------------ correlative search (f-3) ------
@@ -1719,42 +1751,40 @@ int randt_search_global(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, 
         keys.insert(keys.end(), key, key + 9);
       }
   // association once at the guess (frozen for the whole search, quirk A.7-8)
-  randt_matcher_params amp = *mp;
-  amp.n_neighbours = k;
-  const size_t corr_bytes = sizeof(int32_t) * (size_t)moving->v.cap * k;
   double min_cost = 100000.0;
   double best[4] = {1.0, 0.0, 0.0, 0.0};
   int evals = 0;
-  void* d_blk = nullptr;  // [guess4 | idx | n_res] + corr live in a pooled block of their own (ws is used for poses / costs)
-  size_t blk_bytes = 0;
-  RANDT_HIP_CHECK(ctx, randt_dev_alloc(ctx, &d_blk, 256 + corr_bytes, &blk_bytes));
-  double* d_guess = (double*)d_blk;
-  int32_t* d_idx = (int32_t*)((char*)d_blk + 64);
-  int32_t* d_nres = d_idx + 4;
-  int32_t* d_corr = (int32_t*)((char*)d_blk + 256);
-  int32_t h_idx[2] = {fixed_idx, moving_idx};
-  int rc = RANDT_OK;
-  hipError_t e = hipMemcpyAsync(d_guess, h_trans4, sizeof(double) * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_idx, h_idx, sizeof(h_idx), hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) rc = randt_set_error(ctx, RANDT_ERR_HIP, "hipMemcpyAsync", e);
-  if (!rc) rc = launch_associate(ctx, fixed->v, d_idx, moving->v, 0, 1, d_guess, k, mp->lookup_mahalanobis, mp->use_intensity, d_corr, d_idx + 1);
-  while (!rc && !level_nodes.empty()) {
+  // guess | fixed, moving index | residual count | correspondences live in a pooled block of their own (ws holds poses / costs)
+  struct Layout { double* guess; int32_t *idx, *n_res, *corr; };
+  auto layout = [&](Carve& c) {
+    return Layout{c.take<double>(4), c.take<int32_t>(2, 64), c.take<int32_t>(1, 16), c.take<int32_t>((size_t)moving->v.cap * k)};
+  };
+  PooledBlock blk(ctx);
+  RANDT_HIP_CHECK(ctx, blk.alloc(carved_size(layout)));
+  Carve c(blk.p);
+  const Layout L = layout(c);
+  const int32_t h_idx[2] = {fixed_idx, moving_idx};
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.guess, h_trans4, sizeof(double) * 4, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.idx, h_idx, sizeof(h_idx), hipMemcpyHostToDevice, ctx->stream));
+  int rc = launch_associate(ctx, fixed->v, L.idx, moving->v, 0, 1, L.guess, k, mp->lookup_mahalanobis, mp->use_intensity, L.corr, L.idx + 1);
+  if (rc) return rc;
+  while (!level_nodes.empty()) {
     const int P = (int)level_nodes.size();
-    rc = ensure_ws(ctx, (size_t)P * 40 + 64);
-    if (rc) break;
+    struct Level { double *poses, *cost; };
+    auto level = [&](Carve& w) { return Level{w.take<double>(4 * (size_t)P), w.take<double>(P, 8)}; };
+    rc = randt_scratch_reserve(ctx, ctx->ws, carved_size(level));
+    if (rc) return rc;
+    Carve w(ctx->ws.p);
+    const Level V = level(w);
     std::vector<double> h_poses((size_t)P * 4), h_cost(P);
     for (int i = 0; i < P; ++i) memcpy(&h_poses[4 * (size_t)i], level_nodes[i].pose, sizeof(double) * 4);
-    double* d_poses = (double*)ctx->ws;
-    double* d_cost = d_poses + (size_t)P * 4;
     int32_t n_res = 0;
-    e = hipMemcpyAsync(d_poses, h_poses.data(), sizeof(double) * 4 * P, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) { rc = randt_set_error(ctx, RANDT_ERR_HIP, "hipMemcpyAsync", e); break; }
-    rc = launch_eval_cost(ctx, fixed->v, fixed_idx, moving->v, moving_idx, d_corr, k, mp->use_intensity, scale, mp->loss_alpha, d_poses, P, d_cost, d_nres);
-    if (rc) break;
-    e = hipMemcpyAsync(h_cost.data(), d_cost, sizeof(double) * P, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&n_res, d_nres, sizeof(n_res), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = randt_sync(ctx);
-    if (e != hipSuccess) { rc = randt_set_error(ctx, RANDT_ERR_HIP, "cost read-back", e); break; }
+    RANDT_HIP_CHECK(ctx, hipMemcpyAsync(V.poses, h_poses.data(), sizeof(double) * 4 * P, hipMemcpyHostToDevice, ctx->stream));
+    rc = launch_eval_cost(ctx, fixed->v, fixed_idx, moving->v, moving_idx, L.corr, k, mp->use_intensity, scale, mp->loss_alpha, V.poses, P, V.cost, L.n_res);
+    if (rc) return rc;
+    RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_cost.data(), V.cost, sizeof(double) * P, hipMemcpyDeviceToHost, ctx->stream));
+    RANDT_HIP_CHECK(ctx, hipMemcpyAsync(&n_res, L.n_res, sizeof(n_res), hipMemcpyDeviceToHost, ctx->stream));
+    RANDT_HIP_CHECK(ctx, randt_sync(ctx));
     evals += P;
     next_nodes.clear();
     for (int i = 0; i < P; ++i) {   // FIFO order of the reference's queue (:560-605)
@@ -1793,8 +1823,6 @@ int randt_search_global(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, 
     }
     level_nodes.swap(next_nodes);
   }
-  randt_dev_release(ctx, d_blk, blk_bytes);  // every level ended with a synchronisation: nothing reads it any more
-  if (rc) return rc;
   memcpy(h_trans4, best, sizeof(best));  // trans = best_trans (identity if nothing qualified), :606
   if (min_cost_out) *min_cost_out = min_cost;
   if (n_evals) *n_evals = evals;
@@ -1923,6 +1951,13 @@ int randt_predict_state_batch(const randt_state* last, int n, double stamp, int 
   return RANDT_OK;
 }
 
+// The host / device image of a window batch: [ states | results | guess | fixed idx | moving idx | descriptors ], carved
+// alike in pinned memory and in the workspace.
+struct WinImage {
+  double* states; randt_result* res; double* guess; int32_t *fixed_idx, *moving_idx; WinDesc* desc;
+  size_t back_bytes, bytes;  // [ states | results ], the whole image
+};
+
 // n_windows fixed-lag windows of ONE shape (the same number of states and of fixed maps: replicas in lock-step) in one
 // association launch + one solve launch (a workgroup per window), one pinned image up and one back, one synchronisation.
 // Arrays are window-major: h_fixed_idx[w][n_fixed], h_moving_idx[w][S], h_states[w][n_states], h_imu[w][S], h_trans4[w][4].
@@ -1961,49 +1996,43 @@ static int register_windows(randt_ctx* ctx, int n_windows, const randt_maps* fix
   const size_t NT = (size_t)n_windows * T;
   if (NT * moving->v.cap * k > 0x7fffffffull) return randt_set_error(ctx, RANDT_ERR_UNSUPPORTED, "window batch: correspondence tables beyond 2^31 entries", hipSuccess);
 
-  // device workspace: corr | [ states | results | guess | fixed idx | moving idx | descriptors ] -- the bracketed span is ONE
-  // host image, staged in pinned memory and moved with one copy per direction: all of it up, [ states | results ] back
-  // (five small pageable copies cost ~40 us per scan)
+  // device workspace: corr | image.  The image is staged in pinned memory and moved with one copy per direction: all of it up,
+  // [ states | results ] back into a second image (five small pageable copies cost ~40 us per scan)
   const size_t st_stride = 12 * RANDT_WIN_MAX_STATES;  // doubles per window (window.hip, ST_STRIDE x states)
   const size_t corr_stride = (size_t)T * moving->v.cap * k;
-  const size_t corr_bytes = sizeof(int32_t) * corr_stride * n_windows;
-  const size_t off_states = (corr_bytes + 255) & ~(size_t)255;
-  const size_t res_bytes = sizeof(randt_result) * n_windows;
-  const size_t off_res = off_states + sizeof(double) * st_stride * n_windows;
-  const size_t off_guess = off_res + res_bytes;
-  const size_t off_fidx = off_guess + sizeof(double) * 4 * NT;
-  const size_t off_midx = off_fidx + ((sizeof(int32_t) * NT + 63) & ~(size_t)63);
-  const size_t off_desc = (off_midx + sizeof(int32_t) * NT + 255) & ~(size_t)255;
-  const size_t up_span = off_desc + sizeof(WinDesc) * n_windows - off_states;
-  const size_t back_span = off_guess - off_states;  // states | results
-  int rc = ensure_ws(ctx, off_states + up_span + 64);
+  auto image = [&](Carve& c) {
+    WinImage I;
+    I.states = c.take<double>(st_stride * n_windows);
+    const size_t start = c.off - sizeof(double) * st_stride * n_windows;
+    I.res = c.take<randt_result>(n_windows, 64);
+    I.back_bytes = c.off - start;
+    I.guess = c.take<double>(4 * NT, 64);
+    I.fixed_idx = c.take<int32_t>(NT, 64);
+    I.moving_idx = c.take<int32_t>(NT, 64);
+    I.desc = c.take<WinDesc>(n_windows);
+    I.bytes = c.off - start;
+    return I;
+  };
+  struct DeviceLayout { int32_t* corr; WinImage image; };
+  auto device = [&](Carve& c) { return DeviceLayout{c.take<int32_t>(corr_stride * n_windows), image(c)}; };
+  struct HostLayout { WinImage up, back; };
+  auto host = [&](Carve& c) { return HostLayout{image(c), image(c)}; };
+  int rc = randt_scratch_reserve(ctx, ctx->ws, carved_size(device));
   if (rc) return rc;
-  const size_t pin_need = up_span + back_span + 512;
-  if (pin_need > ctx->h_pin_bytes) {
-    if (ctx->h_pin) {
-      RANDT_HIP_CHECK(ctx, randt_sync(ctx));
-      (void)hipHostFree(ctx->h_pin);
-      ctx->h_pin = nullptr;
-      ctx->h_pin_bytes = 0;
-    }
-    const size_t want = pin_need < 16384 ? 16384 : pin_need + pin_need / 2;
-    RANDT_HIP_CHECK(ctx, hipHostMalloc(&ctx->h_pin, want, hipHostMallocDefault));
-    ctx->h_pin_bytes = want;
-  }
-  char* ws = (char*)ctx->ws;
-  char* img = (char*)ctx->h_pin;  // upload image; the download lands behind it
-  char* back = img + ((up_span + 255) & ~(size_t)255);
-  memset(img, 0, up_span);
-  double* h_guess = reinterpret_cast<double*>(img + (off_guess - off_states));
-  int32_t* h_fi = reinterpret_cast<int32_t*>(img + (off_fidx - off_states));
-  int32_t* h_mi = reinterpret_cast<int32_t*>(img + (off_midx - off_states));
-  WinDesc* h_desc = reinterpret_cast<WinDesc*>(img + (off_desc - off_states));
+  rc = randt_scratch_reserve(ctx, ctx->h_pin, carved_size(host));
+  if (rc) return rc;
+  Carve dc(ctx->ws.p), hc(ctx->h_pin.p);
+  const DeviceLayout dev = device(dc);
+  const HostLayout pin = host(hc);
+  int32_t* d_corr = dev.corr;
+  const WinImage &D = dev.image, &up = pin.up, &back = pin.back;
+  memset(up.states, 0, up.bytes);
   for (int w = 0; w < n_windows; ++w) {
     const randt_state* st = h_states + (size_t)w * n_states;
     const int32_t* fidx = h_fixed_idx + (size_t)w * n_fixed;
     const int32_t* midx = h_moving_idx + (size_t)w * S;
     const double* imu = h_imu ? h_imu + (size_t)w * S : nullptr;
-    WinDesc& W = h_desc[w];
+    WinDesc& W = up.desc[w];
     W.S = S;
     W.vec = vec ? 1 : 0;
     W.pad_ = mp->parameterization == RANDT_PARAM_ANALYTIC ? 1 : 0;  // the NDT functor's analytic rotation Jacobian (launch_solve_window picks the instantiation)
@@ -2037,11 +2066,11 @@ static int register_windows(randt_ctx* ctx, int n_windows, const randt_maps* fix
         W.term_state[q] = j;
         W.term_moving[q] = midx[j - 1];
         W.term_fixed[q] = fidx[f];
-        h_fi[(size_t)w * T + q] = fidx[f];
-        h_mi[(size_t)w * T + q] = midx[j - 1];
-        memcpy(h_guess + 4 * ((size_t)w * T + q), st[j].pose, sizeof(double) * 4);  // association at the state's own pose (:364)
+        up.fixed_idx[(size_t)w * T + q] = fidx[f];
+        up.moving_idx[(size_t)w * T + q] = midx[j - 1];
+        memcpy(up.guess + 4 * ((size_t)w * T + q), st[j].pose, sizeof(double) * 4);  // association at the state's own pose (:364)
       }
-    double* h_packed = reinterpret_cast<double*>(img) + st_stride * w;
+    double* h_packed = up.states + st_stride * w;
     for (int j = 0; j <= S; ++j) {  // 12 doubles per state (window.hip, ST_STRIDE)
       double* o = h_packed + 12 * j;
       if (vec) {  // the parameters are pos and rot; the pose slots carry cos / sin of rot for the NDT pass
@@ -2055,21 +2084,19 @@ static int register_windows(randt_ctx* ctx, int n_windows, const randt_maps* fix
     }
   }
   // (the window descriptors are indexed dynamically by the kernel: they live in device memory, not in kernel arguments)
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(ws + off_states, img, up_span, hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_associate(ctx, fixed->v, (const int32_t*)(ws + off_fidx), moving->v, 0, (int)NT, (const double*)(ws + off_guess), k, mp->lookup_mahalanobis,
-                        mp->use_intensity, (int32_t*)ws, (const int32_t*)(ws + off_midx));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(D.states, up.states, up.bytes, hipMemcpyHostToDevice, ctx->stream));
+  rc = launch_associate(ctx, fixed->v, D.fixed_idx, moving->v, 0, (int)NT, D.guess, k, mp->lookup_mahalanobis, mp->use_intensity, d_corr, D.moving_idx);
   if (rc) return rc;
-  rc = launch_solve_window(ctx, fixed->v, moving->v, h_desc[0], (const WinDesc*)(ws + off_desc), (const int32_t*)ws, mp, (double*)(ws + off_states),
-                           (randt_result*)(ws + off_res), n_windows, (int)corr_stride, (int)st_stride);
+  rc = launch_solve_window(ctx, fixed->v, moving->v, up.desc[0], D.desc, d_corr, mp, D.states, D.res, n_windows, (int)corr_stride, (int)st_stride);
   if (rc) return rc;
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(back, ws + off_states, back_span, hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(back.states, D.states, D.back_bytes, hipMemcpyDeviceToHost, ctx->stream));
   RANDT_HIP_CHECK(ctx, randt_sync(ctx));
   for (int w = 0; w < n_windows; ++w) {
     randt_state* st = h_states + (size_t)w * n_states;
     double* trans4 = h_trans4 + 4 * (size_t)w;
     const double prior_t[2] = {trans4[2], trans4[3]};
     const double prior_rot = atan2(trans4[1], trans4[0]);
-    const double* h_packed = reinterpret_cast<const double*>(back) + st_stride * w;
+    const double* h_packed = back.states + st_stride * w;
     for (int j = 0; j <= S; ++j) {
       const double* o = h_packed + 12 * j;
       st[j].lin_vel[0] = o[4]; st[j].lin_vel[1] = o[5]; st[j].rot_vel = o[6];
@@ -2107,7 +2134,7 @@ static int register_windows(randt_ctx* ctx, int n_windows, const randt_maps* fix
     }
     memcpy(trans4, st[S].pose, sizeof(double) * 4);
     if (rejected) rejected[w] = rej;
-    if (h_results) memcpy(&h_results[w], back + (off_res - off_states) + sizeof(randt_result) * w, sizeof(randt_result));
+    if (h_results) memcpy(&h_results[w], &back.res[w], sizeof(randt_result));
   }
   return RANDT_OK;
 }

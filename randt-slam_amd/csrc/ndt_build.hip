@@ -716,24 +716,15 @@ int launch_ndt_build(randt_ctx* ctx, const float* d_points, int n_scans, int pit
   if (pitch > 7168 || ctx->build_tiled || d_polar) {  // pNDT cells: always the tiled path (its statistics kernel carries the option)
     // scans beyond one workgroup's LDS: multi-workgroup stable counting sort in global memory (ndt_build_big.hip)
     if ((long long)pitch > (1ll << 26)) return randt_set_error(ctx, RANDT_ERR_UNSUPPORTED, "scan too large (max 2^26 points)", hipSuccess);
-    const size_t want = ndt_build_big_ws_bytes(n_scans, pitch, d_polar ? 1 : 0);
-    if (want > ctx->build_ws_bytes) {
-      if (ctx->build_ws) {
-        RANDT_HIP_CHECK(ctx, randt_sync(ctx));
-        RANDT_HIP_CHECK(ctx, randt_hip_free(ctx, ctx->build_ws));
-        ctx->build_ws = nullptr;
-        ctx->build_ws_bytes = 0;
-      }
-      RANDT_HIP_CHECK(ctx, randt_hip_malloc(ctx, &ctx->build_ws, want));
-      ctx->build_ws_bytes = want;
-    }
-    int rc = launch_ndt_build_big(ctx, d_points, n_scans, pitch, d_n_points, stride, ioff, cp, out, first_map, ctx->build_ws, d_polar, beam_cov9);
+    int rc = randt_scratch_reserve(ctx, ctx->build_ws, ndt_build_big_ws_bytes(n_scans, pitch, d_polar ? 1 : 0));
+    if (rc) return rc;
+    rc = launch_ndt_build_big(ctx, d_points, n_scans, pitch, d_n_points, stride, ioff, cp, out, first_map, ctx->build_ws.p, d_polar, beam_cov9);
     if (rc) return rc;
     // The tiled path keeps <= 8192 label bins per tile.  A scan whose labels span more (points many times max_range away from
     // the sensor, a cluster grid of more than ~7900 clusters) is refused by it on the device; that is learnt here -- one
     // synchronisation on this cold path -- and such scans are built again through the sorting path (ndt_build_big.hip).
     std::vector<int32_t> st((size_t)4 * n_scans);
-    RANDT_HIP_CHECK(ctx, hipMemcpyAsync(st.data(), ctx->build_ws, sizeof(int32_t) * 4 * n_scans, hipMemcpyDeviceToHost, ctx->stream));
+    RANDT_HIP_CHECK(ctx, hipMemcpyAsync(st.data(), ctx->build_ws.p, sizeof(int32_t) * 4 * n_scans, hipMemcpyDeviceToHost, ctx->stream));
     RANDT_HIP_CHECK(ctx, randt_sync(ctx));
     std::vector<int32_t> npts;
     for (int s = 0; s < n_scans; ++s) {
@@ -800,20 +791,9 @@ int launch_ndt_build(randt_ctx* ctx, const float* d_points, int n_scans, int pit
     lds = fixed_bytes + aux;
   }
   // fallback scratch: 2 x npad label words per scan
-  {
-    const size_t want = sizeof(int32_t) * 2 * (size_t)npad * n_scans + 256;
-    if (want > ctx->build_ws_bytes) {
-      if (ctx->build_ws) {
-        RANDT_HIP_CHECK(ctx, randt_sync(ctx));
-        RANDT_HIP_CHECK(ctx, randt_hip_free(ctx, ctx->build_ws));
-        ctx->build_ws = nullptr;
-        ctx->build_ws_bytes = 0;
-      }
-      RANDT_HIP_CHECK(ctx, randt_hip_malloc(ctx, &ctx->build_ws, want + want / 4));
-      ctx->build_ws_bytes = want + want / 4;
-    }
-  }
-  int32_t* d_fallback = reinterpret_cast<int32_t*>(ctx->build_ws);
+  const int ws_rc = randt_scratch_reserve(ctx, ctx->build_ws, sizeof(int32_t) * 2 * (size_t)npad * n_scans + 256);
+  if (ws_rc) return ws_rc;
+  int32_t* d_fallback = static_cast<int32_t*>(ctx->build_ws.p);
   // Atomic ranking (see k_ndt_build): every launch checks the serving order it relies on and falls back in-kernel; the
   // workgroups that had to are counted in a host-visible word, read here without a synchronisation -- once it is non-zero the
   // context ranks with ballots only.

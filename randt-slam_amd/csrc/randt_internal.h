@@ -28,20 +28,54 @@ struct MapView {
   double res, offset_x, offset_y;
 };
 
+// A grow-only buffer of a context (randt_scratch_reserve, api.hip): device memory, or pinned host memory.
+struct Scratch {
+  void* p = nullptr;
+  size_t bytes = 0;
+  bool pinned = false;
+};
+
+// Bump layout of one allocation.  A layout is described ONCE, as a function of a Carve that fills a struct of typed pointers:
+// run on a null base it gives the size to reserve, run on the real base the pointers.
+struct Carve {
+  char* base;
+  size_t off = 0;
+  explicit Carve(void* b) : base(static_cast<char*>(b)) {}
+  template <class T>
+  T* take(size_t n, size_t align = 256) {
+    off = (off + align - 1) & ~(align - 1);
+    T* p = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + off);
+    off += sizeof(T) * n;
+    return p;
+  }
+  size_t size() const { return (off + 255) & ~(size_t)255; }  // bytes carved so far
+};
+template <class F>
+size_t carved_size(F&& layout) {  // the bytes a layout needs: what it carves from a null base
+  Carve c(nullptr);
+  layout(c);
+  return c.size();
+}
+
+// Device words of the synchronous host-level conveniences, one member per entry point: they call each other and the batch
+// entries, so each touches its own member only.  (16-byte alignment: the kernels read poses as double2.)
+struct SmallScratch {
+  struct alignas(64) { int32_t status[2]; } append;
+  struct alignas(64) { alignas(16) double pose[4]; randt_result res; int32_t fixed_idx; } pair;
+  struct alignas(64) { alignas(16) double pose[4]; int32_t fixed_idx; double out; double terms[3]; } cs;
+};
+
 struct randt_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   std::string last_error;
   // scratch (grown on demand, never inside a timed region after warm-up)
-  void* ws = nullptr;
-  size_t ws_bytes = 0;
-  void* h_pin = nullptr;     // pinned host memory: staging image of the window entries (one copy per direction), grown on demand
-  size_t h_pin_bytes = 0;
-  void* small = nullptr;     // 4 KB of device scratch for the synchronous host-level conveniences (lazily allocated)
-  void* build_ws = nullptr;  // label scratch of k_ndt_build's fallback sort (its own buffer: callers stage points in ws)
-  size_t build_ws_bytes = 0;
-  void* build_wide_ws = nullptr;  // tiled build, scans whose labels span more than a tile's bins: sort workspace (ndt_build_big.hip)
-  size_t build_wide_ws_bytes = 0;
+  Scratch ws;                        // workspace of the entry points: staged inputs, correspondence tables, partial sums
+  Scratch h_pin{nullptr, 0, true};   // pinned host memory: staging images of the window entries (one copy per direction)
+  Scratch build_ws;                  // label scratch of k_ndt_build's fallback sort, status words + workspace of the tiled build
+  Scratch build_wide_ws;             // tiled build, scans whose labels span more than a tile's bins: sort workspace (ndt_build_big.hip)
+  Scratch order_ws;                  // k_solve_order's size-sorted order of the registrations (int32 each)
+  SmallScratch* small = nullptr;     // lazily allocated (api.hip, small_block)
   double* d_trace = nullptr;
   int trace_len = 0;
   int lds_limit = 160 * 1024;
@@ -53,8 +87,6 @@ struct randt_ctx {
   int solve_group = -1;      // the one-wavefront solve's workgroups take their registrations through k_solve_order's size-sorted order:
                              // -1 = for launches of >= 8 registrations per compute unit, 0 / 1 = never / always (RANDT_SOLVE_GROUP;
                              // round-5 experiment, profiles/experiments/r05_solve_length_grouping.md)
-  void* order_ws = nullptr;  // the order itself (int32 per registration, grown on demand)
-  size_t order_ws_bytes = 0;
   int solve_split = -1;      // wavefronts per registration in the pair solve: -1 = chosen from the batch size (solve.hip, split_width),
                              // 0 = never split, 2..8 = forced (RANDT_SOLVE_SPLIT; experiments)
   int solve_mode = 0;        // RANDT_SOLVE_AUTO / RANDT_SOLVE_THROUGHPUT / RANDT_SOLVE_LATENCY (randt_ctx_set_solve_mode)
@@ -121,6 +153,8 @@ void randt_dev_release(randt_ctx* ctx, void* p, size_t bytes);                  
 hipError_t randt_hip_malloc(randt_ctx* ctx, void** p, size_t bytes);  // plain hipMalloc, counted (grow-only workspaces)
 hipError_t randt_hip_free(randt_ctx* ctx, void* p);
 hipError_t randt_sync(randt_ctx* ctx);                                // hipStreamSynchronize(ctx->stream), counted
+// makes `s` hold at least `bytes` (contents are lost when it grows; on failure it is left empty)
+__attribute__((visibility("hidden"))) int randt_scratch_reserve(randt_ctx* ctx, Scratch& s, size_t bytes);
 // bytes of pinned host memory the device can read under the same address, valid until the stream has passed the work
 // enqueued next; nullptr if the request is larger than a segment (callers fall back to a pageable copy + synchronisation)
 void* randt_pin_take(randt_ctx* ctx, size_t bytes);
@@ -153,6 +187,8 @@ struct SolveParams {
   double ftol, gtol, ptol, r0, rmax, rmin, min_rel, dmin, dmax;
   int32_t gnc_steps, max_it, k, max_invalid;
 };
+
+__attribute__((visibility("hidden"))) SolveParams randt_solve_params(const randt_matcher_params* mp);  // api.hip
 
 int randt_set_error(randt_ctx* ctx, int status, const char* what, hipError_t e);
 #define RANDT_HIP_CHECK(ctx, call)                                          \

@@ -727,19 +727,10 @@ int launch_cfg(randt_ctx* ctx, const MapView& fixed, const int32_t* d_fixed_idx,
   // sort is taken from eight registrations per compute unit upwards (RANDT_SOLVE_GROUP = 0 / 1: never / always)
   const bool grouped = ctx->solve_group < 0 ? n_pairs >= 8 * ctx->n_cus : ctx->solve_group > 0;
   if (RPB > 1 && grouped && n_pairs >= 2 * RPB) {
-    const size_t need = sizeof(int32_t) * (size_t)n_pairs;
-    if (need > ctx->order_ws_bytes) {
-      if (ctx->order_ws) {
-        RANDT_HIP_CHECK(ctx, randt_sync(ctx));
-        RANDT_HIP_CHECK(ctx, randt_hip_free(ctx, ctx->order_ws));
-        ctx->order_ws = nullptr;
-        ctx->order_ws_bytes = 0;
-      }
-      RANDT_HIP_CHECK(ctx, randt_hip_malloc(ctx, &ctx->order_ws, need + need / 2 + 256));
-      ctx->order_ws_bytes = need + need / 2 + 256;
-    }
-    hipLaunchKernelGGL(k_solve_order, dim3(1), dim3(1024), 0, ctx->stream, moving, moving_first, n_pairs, P.k, static_cast<int32_t*>(ctx->order_ws));
-    d_order = static_cast<const int32_t*>(ctx->order_ws);
+    const int rc = randt_scratch_reserve(ctx, ctx->order_ws, sizeof(int32_t) * (size_t)n_pairs);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_solve_order, dim3(1), dim3(1024), 0, ctx->stream, moving, moving_first, n_pairs, P.k, static_cast<int32_t*>(ctx->order_ws.p));
+    d_order = static_cast<const int32_t*>(ctx->order_ws.p);
   }
   hipLaunchKernelGGL((k_solve<D, PARAM, BLOCK, AM2, RPB>), dim3((n_pairs + RPB - 1) / RPB), dim3(BLOCK * RPB), 0, ctx->stream, fixed,
                      d_fixed_idx, moving, moving_first, d_corr, P, d_pose4, d_results, ctx->d_trace, ctx->trace_len, n_pairs, d_order);
@@ -800,27 +791,7 @@ int launch_solve(randt_ctx* ctx, const MapView& fixed, const int32_t* d_fixed_id
                  int moving_first, int n_pairs, const int32_t* d_corr, const randt_matcher_params* mp,
                  double* d_pose4, randt_result* d_results) {
   if (n_pairs <= 0) return RANDT_OK;
-  SolveParams P;
-  P.loss_a = mp->loss_scale;
-  P.mu_scale = mp->mu_scale;
-  P.alpha = mp->loss_alpha;
-  P.weight = mp->loss_weight;
-  P.gnc_div = mp->gnc_divisor;
-  P.mu_cap = pow(mp->gnc_divisor, (double)(mp->gnc_steps - 1));
-  P.mu_stop = 1.0 / sqrt(mp->gnc_divisor);
-  P.ftol = mp->function_tolerance;
-  P.gtol = mp->gradient_tolerance;
-  P.ptol = mp->parameter_tolerance;
-  P.r0 = mp->initial_radius;
-  P.rmax = mp->max_radius;
-  P.rmin = mp->min_radius;
-  P.min_rel = mp->min_relative_decrease;
-  P.dmin = mp->min_lm_diagonal;
-  P.dmax = mp->max_lm_diagonal;
-  P.gnc_steps = mp->gnc_steps;
-  P.max_it = mp->max_iterations;
-  P.k = mp->n_neighbours;
-  P.max_invalid = mp->max_consecutive_invalid_steps;
+  const SolveParams P = randt_solve_params(mp);
   if (P.k <= 0) return randt_set_error(ctx, RANDT_ERR_INVALID, "n_neighbours must be > 0", hipSuccess);
   const int block = ctx->solve_block;
   const int d3 = mp->use_intensity ? 1 : 0;

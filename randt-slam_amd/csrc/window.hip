@@ -1135,27 +1135,7 @@ int launch_solve_window(randt_ctx* ctx, const MapView& fixed, const MapView& mov
                         int corr_stride, int state_stride) {
   randt_note_enqueue(ctx);  // (RANDT_SOLVE_AUTO of the process's other contexts: this one has work in flight)
   if (n_windows <= 0) return RANDT_OK;
-  SolveParams P;
-  P.loss_a = mp->loss_scale;
-  P.mu_scale = mp->mu_scale;
-  P.alpha = mp->loss_alpha;
-  P.weight = mp->loss_weight;
-  P.gnc_div = mp->gnc_divisor;
-  P.mu_cap = pow(mp->gnc_divisor, (double)(mp->gnc_steps - 1));
-  P.mu_stop = 1.0 / sqrt(mp->gnc_divisor);
-  P.ftol = mp->function_tolerance;
-  P.gtol = mp->gradient_tolerance;
-  P.ptol = mp->parameter_tolerance;
-  P.r0 = mp->initial_radius;
-  P.rmax = mp->max_radius;
-  P.rmin = mp->min_radius;
-  P.min_rel = mp->min_relative_decrease;
-  P.dmin = mp->min_lm_diagonal;
-  P.dmax = mp->max_lm_diagonal;
-  P.gnc_steps = mp->gnc_steps;
-  P.max_it = mp->max_iterations;
-  P.k = mp->n_neighbours;
-  P.max_invalid = mp->max_consecutive_invalid_steps;
+  const SolveParams P = randt_solve_params(mp);
   // more than three optimised states (no shipped configuration): the general kernel
   if (desc.n_tan > WIN_NMAX || desc.S > WIN_SMAX || desc.n_terms > 6 || ctx->window_general)
     return launch_solve_window_gen(ctx, fixed, moving, desc, d_desc, d_corr, P, d_states, d_result, n_windows, corr_stride, state_stride);
