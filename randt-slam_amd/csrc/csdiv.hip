@@ -224,12 +224,13 @@ __global__ __launch_bounds__(CS_PBLOCK) void k_cs_pair(MapView fixed, const int3
 int launch_cs_divergence(randt_ctx* ctx, const MapView& fixed, int fixed_first, int fixed_count, const int32_t* d_fixed_idx,
                          const MapView& moving, int moving_first, int n_pairs, const double* d_pose4, double* d_partial,
                          double* d_out, double* d_terms) {
-  randt_note_enqueue(ctx);  // (RANDT_SOLVE_AUTO of the process's other contexts: this one has work in flight)
-  const int max_tiles = (fixed.cap + CS_SELF_OUTER - 1) / CS_SELF_OUTER;
-  hipLaunchKernelGGL(k_cs_self, dim3(max_tiles, fixed_count), dim3(CS_BLOCK), 0, ctx->stream, fixed, fixed_first, max_tiles, d_partial);
+  // refusals come first: a refused call launches no kernel
   const size_t lds = (size_t)moving.cap * (9 * 4 + 4);  // transformed moving cells + their validity flags
   if (lds + 12 * 1024 > (size_t)ctx->lds_limit)  // (+ the kernel's static tile of fixed cells: 10.3 KB)
     return randt_set_error(ctx, RANDT_ERR_UNSUPPORTED, "moving-map capacity too large for the CS-divergence kernel", hipSuccess);
+  randt_note_enqueue(ctx);  // (RANDT_SOLVE_AUTO of the process's other contexts: this one has work in flight)
+  const int max_tiles = (fixed.cap + CS_SELF_OUTER - 1) / CS_SELF_OUTER;
+  hipLaunchKernelGGL(k_cs_self, dim3(max_tiles, fixed_count), dim3(CS_BLOCK), 0, ctx->stream, fixed, fixed_first, max_tiles, d_partial);
   RANDT_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_cs_pair), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_cs_pair, dim3(n_pairs), dim3(CS_PBLOCK), lds, ctx->stream, fixed, d_fixed_idx, moving, moving_first, d_pose4,
                      d_partial, fixed_first, max_tiles, d_out, d_terms);

@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import csdiv_ref
 import randt_slam_amd as R
 from randt_slam_amd import synth
 
@@ -313,29 +314,9 @@ def test_cs_divergence_vs_numpy_definition(env):
     fc = rand_cells(60)
     mc = rand_cells(50, centres=[f["mean"].astype(np.float64) for f in fc])
 
-    def full(c):
-        c = c.astype(np.float64)
-        return np.array([[c[0], c[1], c[2]], [c[1], c[3], c[4]], [c[2], c[4], c[5]]])
-
-    def pair(a, b):
-        S = full(a["cov"]) + full(b["cov"])
-        d = a["mean"].astype(np.float64) - b["mean"].astype(np.float64)
-        return 0.5 / np.sqrt(np.pi ** 2 * np.linalg.det(S)) * np.exp(-0.5 * d @ np.linalg.solve(S, d))
-
-    def own(cells):
-        t = 0.0
-        for i, a in enumerate(cells):
-            det = np.linalg.det(full(a["cov"]))
-            assert abs(det / 1e-5 - 1.0) > 0.05            # no cell sits on the gate, where fp32 and fp64 could disagree
-            if det < 1e-5:
-                continue
-            t += np.sqrt(np.linalg.det(np.linalg.inv(full(a["cov"])))) / (2 * np.pi)
-            t += sum(2 * pair(a, cells[j]) for j in range(i))
-        return t
-
-    inter = sum(pair(a, b) for a in fc if np.linalg.det(full(a["cov"])) >= 1e-5 for b in mc)
-    ref_terms = np.array([inter, own(fc), own(mc)])
-    ref = -np.log(inter) + 0.5 * np.log(ref_terms[1]) + 0.5 * np.log(ref_terms[2])
+    # the definition itself lives in csdiv_ref.py (shared with test_gpu_csdiv_shapes.py); it asserts that no cell sits within
+    # 5 % of the gate, where fp32 and fp64 could disagree
+    ref, ref_terms = csdiv_ref.cs_definition(fc, mc)
     mapp = R.indoor_map_params()
     fm = R.Maps(ctx, 1, mapp, 64, with_grid=True)
     fm.upload(0, fc)
@@ -347,7 +328,7 @@ def test_cs_divergence_vs_numpy_definition(env):
     ident = torch.tensor([[1.0, 0.0, 0.0, 0.0]], dtype=torch.float64, device=dev)
     host.cs_divergence_batch(ctx, fm, 0, 1, torch.zeros(1, dtype=torch.int32, device=dev), mm, 0, 1, ident, out, terms)
     ctx.synchronize()
-    assert sum(np.linalg.det(full(a["cov"])) < 1e-5 for a in fc) >= 3
+    assert (~csdiv_ref.valid_cells(fc)).sum() >= 3
     got = terms.cpu().numpy()[0]
     assert np.isclose(got[0], ref_terms[0], rtol=3e-5), (got, ref_terms)                # fp32 pair terms (Sf + Sq is well conditioned)
     # the maps' own terms hold sqrt(det(S^-1)) of single cells: the reference's float cofactor determinant of a covariance
