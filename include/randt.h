@@ -376,6 +376,12 @@ int randt_scan_register_batch_dev(randt_ctx* ctx, const float* d_points, int n_s
 int randt_register_pair(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, const randt_maps* moving,
                         int moving_idx, const randt_matcher_params* mp, double h_pose4[4], randt_result* h_result);
 
+/* Host convenience: n_pairs pairs in one launch, synchronous -- pair p = moving map moving_first + p against fixed map
+ * h_fixed_idx[p]; h_pose4 [n_pairs][4] in/out and h_results [n_pairs] (nullable) are host arrays.  Every pair's answer is
+ * randt_register_pair's. */
+int randt_register_pairs(randt_ctx* ctx, const randt_maps* fixed, const int32_t* h_fixed_idx, const randt_maps* moving,
+                         int moving_first, int n_pairs, const randt_matcher_params* mp, double* h_pose4, randt_result* h_results);
+
 /* ------------------------------------------------------------------ correlative search (f-3) - */
 /* csm_* members of NDTMatcherParameters (ndt_slam_parameters.h:76-83). */
 typedef struct randt_bnb_params {
@@ -396,6 +402,32 @@ int randt_search_global(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, 
                         const randt_matcher_params* mp, const randt_bnb_params* bp, double scale,
                         double search_window_size_linear, double search_window_size_angular, double h_trans4[4],
                         double* min_cost_out, int* n_evals);
+
+/* The same search for n_pairs pairs at once, with the level loop on the device: pair p = moving map moving_first + p against
+ * fixed map d_fixed_idx[p] (the convention of randt_register_batch_dev), its own windows h_window_linear[p] /
+ * h_window_angular[p] (host arrays; the csm_* windows cap them as in the single call).  d_trans4 [n_pairs][4] in: guesses,
+ * out: best poses; d_results [n_pairs].  Every answer equals randt_search_global's bit for bit.  Nothing is read back.  The
+ * call only enqueues -- no allocation, no wait -- once the context's workspace has grown to the batch's size, and as long as
+ * the delta-pose tables it uploads fit one 512 KiB pinned segment: 32 B per level-1 grid node of every DISTINCT
+ * (window_linear, window_angular) pair + 8 B per pair, e.g. about 90 distinct 180-node grids.  A larger image is copied from
+ * pageable memory and the call synchronises the stream before it returns.  Workspace: 60 B x n_pairs x max_nodes.
+ * max_nodes bounds the poses one pair may generate over all levels; a pair that would need more stops there with status 1,
+ * its d_trans4 row untouched, and disturbs no other pair. */
+typedef struct randt_bnb_result {
+  double min_cost;  /* the reference's return value; of a pair with status 1: the minimum reached so far */
+  int32_t n_evals;  /* poses evaluated */
+  int32_t status;   /* 0 ok, 1 = max_nodes exceeded */
+} randt_bnb_result; /* 16 B */
+int randt_search_global_batch_dev(randt_ctx* ctx, const randt_maps* fixed, const int32_t* d_fixed_idx, const randt_maps* moving,
+                                  int moving_first, int n_pairs, const randt_matcher_params* mp, const randt_bnb_params* bp,
+                                  double scale, const double* h_window_linear, const double* h_window_angular, int max_nodes,
+                                  double* d_trans4, randt_bnb_result* d_results);
+/* Host convenience, synchronous: host arrays in and out (h_n_evals nullable), max_nodes <= 0 = 8192.  A pair that exceeds
+ * max_nodes is searched again through randt_search_global, so the answers are always the single call's. */
+int randt_search_global_batch(randt_ctx* ctx, const randt_maps* fixed, const int32_t* h_fixed_idx, const randt_maps* moving,
+                              int moving_first, int n_pairs, const randt_matcher_params* mp, const randt_bnb_params* bp,
+                              double scale, const double* h_window_linear, const double* h_window_angular, int max_nodes,
+                              double* h_trans4, double* h_min_cost, int32_t* h_n_evals);
 
 /* ------------------------------------------------------------------ CS divergence (f-2) ------ */
 /* Map::calculateCSDivergence (src/ndt_representation/ndt_map.cpp:42-99) for a batch of pairs: pair p =

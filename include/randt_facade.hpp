@@ -827,6 +827,63 @@ class Matcher {
     return cost;
   }
 
+  // The same batch on ONE context (the fixed maps'), no group: the maps are copied side by side into two batches and
+  // randt_register_pairs registers them in one launch.  Bit-identical to estimateLoopConstraint pair by pair.
+  std::vector<double> estimateLoopConstraintBatch(std::vector<SE2d>& trans, const std::vector<const Map*>& fixed_ndts,
+                                                  const std::vector<int>& fixed_of_pair, const std::vector<const Map*>& moving_ndts,
+                                                  int max_gnc_steps, bool use_intensity_as_dimension, double scale) const {
+    const int n_pairs = static_cast<int>(moving_ndts.size());
+    std::vector<double> cost(static_cast<size_t>(n_pairs), failed_value());
+    PairBatches b;
+    randt_matcher_params mp;
+    if (!stage_pairs(trans, fixed_ndts, fixed_of_pair, moving_ndts, "estimateLoopConstraintBatch", &b)) return cost;
+    if (!loop_params(max_gnc_steps, use_intensity_as_dimension, scale, &mp, b.ctx)) return cost;
+    std::vector<randt_result> res(static_cast<size_t>(n_pairs));
+    const int rc = randt_register_pairs(b.ctx, b.fixed, b.fidx.data(), b.moving, 0, n_pairs, &mp, b.pose.data(), res.data());
+    if (!facade_check(rc, "randt_register_pairs", b.ctx)) return cost;
+    for (int p = 0; p < n_pairs; ++p) {
+      if (res[p].n_residuals == 0) std::cout << "WARNING: NO RESIDUALS ADDED!" << std::endl;  // pose untouched, like the single call
+      std::copy(b.pose.begin() + 4 * p, b.pose.begin() + 4 * p + 4, trans[p].d);
+      cost[p] = res[p].cost;
+    }
+    return cost;
+  }
+
+  // NOT in the reference: estimateTransformGlobalBNB for a batch of independent pairs on ONE context, the level loop of the
+  // search on the device (randt_search_global_batch).  Pair p searches *moving_ndts[p] against *fixed_ndts[fixed_of_pair[p]]
+  // from trans[p] (in/out) in its own windows; every answer is the single call's bit for bit.  Returns the minimum costs.
+  std::vector<double> estimateTransformGlobalBNBBatch(std::vector<SE2d>& trans, const std::vector<const Map*>& fixed_ndts,
+                                                      const std::vector<int>& fixed_of_pair, const std::vector<const Map*>& moving_ndts,
+                                                      bool use_intensity_as_dimension, double scale, const std::vector<double>& windows_linear,
+                                                      const std::vector<double>& windows_angular) const {
+    const int n_pairs = static_cast<int>(moving_ndts.size());
+    std::vector<double> cost(static_cast<size_t>(n_pairs), failed_value());
+    PairBatches b;
+    if (static_cast<int>(windows_linear.size()) != n_pairs || static_cast<int>(windows_angular.size()) != n_pairs) {
+      facade_check(RANDT_ERR_INVALID, "estimateTransformGlobalBNBBatch: one window pair per pair", nullptr);
+      return cost;
+    }
+    if (!stage_pairs(trans, fixed_ndts, fixed_of_pair, moving_ndts, "estimateTransformGlobalBNBBatch", &b)) return cost;
+    randt_bnb_params csm{};
+    csm.csm_window_linear = parameters_.csm_window_linear;
+    csm.csm_window_angular = parameters_.csm_window_angular;
+    csm.csm_linear_step = parameters_.csm_linear_step;
+    csm.csm_cost_threshold = parameters_.csm_cost_threshold;
+    csm.csm_max_px_accurate_range = parameters_.csm_max_px_accurate_range;
+    csm.csm_n_iter = parameters_.csm_n_iter;
+    randt_matcher_params mp;
+    randt_matcher_params_default(&mp);
+    mp.loss_alpha = parameters_.loss_function_convexity;
+    mp.lookup_mahalanobis = parameters_.lookup_mahalanobis ? 1 : 0;
+    mp.use_intensity = use_intensity_as_dimension ? 1 : 0;
+    std::vector<double> min_cost(static_cast<size_t>(n_pairs));
+    const int rc = randt_search_global_batch(b.ctx, b.fixed, b.fidx.data(), b.moving, 0, n_pairs, &mp, &csm, scale, windows_linear.data(),
+                                             windows_angular.data(), 0, b.pose.data(), min_cost.data(), nullptr);
+    if (!facade_check(rc, "randt_search_global_batch", b.ctx)) return cost;
+    for (int p = 0; p < n_pairs; ++p) std::copy(b.pose.begin() + 4 * p, b.pose.begin() + 4 * p + 4, trans[p].d);
+    return min_cost;
+  }
+
   // double Matcher::estimateTransformGlobalBNB(Sophus::SE2d& trans, const Map& fixed_ndt, Map& moving_ndt,
   //   bool use_intensity_as_dimension, double scale, double search_window_size_linear,
   //   double search_window_size_angular)                                       (ndt_matcher.cpp:495-608)
@@ -1072,6 +1129,63 @@ class Matcher {
     stage_ctx_ = ctx;
     return facade_check(rc, "randt_maps_create (window staging)", ctx->get());
   }
+  // the maps of a batch of pairs side by side on the fixed maps' context, destroyed with the object
+  struct PairBatches {
+    randt_ctx* ctx = nullptr;
+    randt_maps *fixed = nullptr, *moving = nullptr;
+    std::vector<int32_t> fidx;
+    std::vector<double> pose;
+    PairBatches() = default;
+    PairBatches(const PairBatches&) = delete;
+    PairBatches& operator=(const PairBatches&) = delete;
+    ~PairBatches() {
+      randt_maps_destroy(fixed);
+      randt_maps_destroy(moving);
+    }
+  };
+  bool stage_pairs(const std::vector<SE2d>& trans, const std::vector<const Map*>& fixed_ndts, const std::vector<int>& fixed_of_pair,
+                   const std::vector<const Map*>& moving_ndts, const char* what, PairBatches* b) const {
+    const int n_pairs = static_cast<int>(moving_ndts.size()), n_fixed = static_cast<int>(fixed_ndts.size());
+    if (n_pairs == 0 || n_fixed == 0 || static_cast<int>(trans.size()) != n_pairs || static_cast<int>(fixed_of_pair.size()) != n_pairs) {
+      facade_check(RANDT_ERR_INVALID, what, nullptr);
+      return false;
+    }
+    for (int f : fixed_of_pair)
+      if (f < 0 || f >= n_fixed) {
+        facade_check(RANDT_ERR_INVALID, what, nullptr);
+        return false;
+      }
+    int fcap = 1, mcap = 1;
+    for (const Map* m : fixed_ndts) fcap = std::max(fcap, m->capacity());
+    for (const Map* m : moving_ndts) mcap = std::max(mcap, m->capacity());
+    for (const Map* m : fixed_ndts)
+      if (std::memcmp(&m->params(), &fixed_ndts[0]->params(), sizeof(randt_map_params)) != 0) {
+        facade_check(RANDT_ERR_INVALID, "batch: the fixed maps must share one geometry (centre, resolution, window)", nullptr);
+        return false;
+      }
+    for (const Map* m : moving_ndts)
+      if (std::memcmp(&m->params(), &moving_ndts[0]->params(), sizeof(randt_map_params)) != 0) {
+        facade_check(RANDT_ERR_INVALID, "batch: the moving maps must share one geometry", nullptr);
+        return false;
+      }
+    b->ctx = fixed_ndts[0]->context()->get();
+    int rc = randt_maps_create(b->ctx, n_fixed, &fixed_ndts[0]->params(), fcap, 1, &b->fixed);
+    if (!rc) rc = randt_maps_create(b->ctx, n_pairs, &moving_ndts[0]->params(), mcap, 0, &b->moving);
+    for (int f = 0; f < n_fixed && !rc; ++f) {
+      if (fixed_ndts[f]->context()->get() != b->ctx) randt_ctx_synchronize(fixed_ndts[f]->context()->get());
+      rc = randt_maps_copy(b->fixed, f, fixed_ndts[f]->handle(), 0, 1);
+    }
+    for (int p = 0; p < n_pairs && !rc; ++p) {
+      if (moving_ndts[p]->context()->get() != b->ctx) randt_ctx_synchronize(moving_ndts[p]->context()->get());
+      rc = randt_maps_copy(b->moving, p, moving_ndts[p]->handle(), 0, 1);
+    }
+    if (!facade_check(rc, what, b->ctx)) return false;
+    b->fidx.assign(fixed_of_pair.begin(), fixed_of_pair.end());
+    b->pose.resize(4 * static_cast<size_t>(n_pairs));
+    for (int p = 0; p < n_pairs; ++p) std::copy(trans[p].d, trans[p].d + 4, b->pose.begin() + 4 * p);
+    return true;
+  }
+
   void release_stage() {
     randt_maps_destroy(stage_fixed_);
     randt_maps_destroy(stage_moving_);

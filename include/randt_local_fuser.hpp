@@ -267,6 +267,86 @@ class LocalFuser {
     return added;
   }
 
+  // NOT in the reference: detectLoopClosuresCovarianceGated() with the candidates of ALL pending queries as one batch on the
+  // fuser's context: one batched correlative search (compute_dfs_loop_closure; the level loop runs on the device), one batched
+  // refinement, then the CS gate; log and edges in the sequential order.  Candidate selection is the sequential method's, the
+  // candidates do not depend on each other and the batched calls are bit-identical to the single ones, so the graph comes out
+  // exactly as from detectLoopClosuresCovarianceGated() called at the same moments.
+  int detectLoopClosuresCovarianceGatedBatched(int* n_candidates = nullptr) {
+    struct Candidate { int q, lid, sub_i; };
+    std::vector<Candidate> cand;
+    std::vector<SE2d> trans;
+    std::vector<double> windows_linear, windows_angular;
+    const double thr = parameters_.max_data_association_mahalanobis_dist;
+    while (!_next_maps_to_search_loop.empty()) {
+      const int q = _next_maps_to_search_loop.front();
+      _next_maps_to_search_loop.pop_front();
+      std::map<int, std::pair<int, double>> best_submap_matches;
+      const Pose& pq = nodes_.at(q);
+      for (const auto& pose_i : nodes_) {
+        const int sub_i = submap_idzs_.at(pose_i.first);
+        if (sub_i == submap_idzs_.at(q) || sub_i == n_finished_submaps_ || !submaps_.count(sub_i)) continue;   // :355
+        const std::array<double, 4>& P = pose_i.second.cov_pos_pos;
+        const double a = P[0], b = P[1], c = P[2], d = P[3], det = a * d - b * c;
+        if (!(a > 0.0 && det > 0.0)) continue;
+        const double dx = pq.pose.d[2] - pose_i.second.pose.d[2], dy = pq.pose.d[3] - pose_i.second.pose.d[3];
+        const double dist = std::sqrt((d * dx * dx - (b + c) * dx * dy + a * dy * dy) / det);                 // :357
+        if (dist < thr) {                                                                                     // :358-362
+          auto it = best_submap_matches.find(sub_i);
+          if (it == best_submap_matches.end() || dist < it->second.second) best_submap_matches[sub_i] = std::make_pair(pose_i.first, dist);
+        }
+      }
+      for (const auto& match : best_submap_matches) {
+        const int sub_i = match.first, lid = match.second.first;
+        cand.push_back({q, lid, sub_i});
+        trans.push_back(se2_mul(se2_inv(nodes_.at(root_nodes_.at(sub_i)).pose), pq.pose));   // :376
+        const std::array<double, 9>& cov = nodes_.at(lid).cov;                                // :379-388
+        const double ca = cov[0], cc = cov[3], cd = cov[4];
+        const double lam0 = 0.5 * (ca + cd) - std::sqrt(0.25 * (ca - cd) * (ca - cd) + cc * cc);
+        windows_linear.push_back(thr * std::abs(lam0));
+        windows_angular.push_back(std::min(2 * M_PI, thr * std::sqrt(cov[8])));
+      }
+    }
+    if (n_candidates) *n_candidates = static_cast<int>(cand.size());
+    if (cand.empty()) return 0;
+    std::vector<const Map*> fixed, moving;
+    std::vector<int> fixed_of_pair;
+    std::map<int, int> slot_of_submap;
+    for (const Candidate& c : cand) {
+      if (!slot_of_submap.count(c.sub_i)) {
+        slot_of_submap[c.sub_i] = static_cast<int>(fixed.size());
+        fixed.push_back(&submaps_.at(c.sub_i));
+      }
+      fixed_of_pair.push_back(slot_of_submap.at(c.sub_i));
+      moving.push_back(&scans_.at(c.q));
+    }
+    if (parameters_.compute_dfs_loop_closure)
+      ndt_matcher_.estimateTransformGlobalBNBBatch(trans, fixed, fixed_of_pair, moving, parameters_.use_intensity_in_loop_closure,
+                                                   parameters_.loop_closure_scale, windows_linear, windows_angular);
+    ndt_matcher_.estimateLoopConstraintBatch(trans, fixed, fixed_of_pair, moving, parameters_.loop_closure_gnc_steps,
+                                             parameters_.use_intensity_in_loop_closure, parameters_.loop_closure_scale);   // :395, all at once
+    int added = 0;
+    for (size_t p = 0; p < cand.size(); ++p) {
+      const Candidate& c = cand[p];
+      Map m_loop_map = scans_.at(c.q);
+      m_loop_map.transformMap(trans[p]);                                                     // :396
+      const double cs = submaps_.at(c.sub_i).calculateCSDivergence(m_loop_map);              // :397
+      const bool ok = cs < parameters_.loop_closure_max_cs_divergence;                       // :402
+      loop_log_.push_back({c.q, c.lid, cs, ok});
+      if (ok) {
+        Constraint e;
+        e.id_begin = root_nodes_.at(c.sub_i);
+        e.id_end = c.q;
+        e.trans = trans[p];
+        const double w = parameters_.loop_closure_weight;
+        e.sqrt_information = {w, 0, 0, 0, w, 0, 0, 0, w};
+        edges_.push_back(e);
+        ++added;
+      }
+    }
+    return added;
+  }
+
   // NDTSlam::optimizePoseGraph (ndt_slam.cpp:351-361) + the pose part of LocalFuser::updateSubmaps (local_fuser.cpp:65-88)
   void optimizePoseGraph() {
     if (nodes_.empty() || edges_.empty() || submap_idzs_.back() <= 0) return;

@@ -20,7 +20,8 @@ RESULT_DTYPE = np.dtype(
      ("n_residuals", "<i4"), ("iterations", "<i4"), ("gnc_solves", "<i4"), ("termination", "<i4"),
      ("n_evals", "<i4"), ("status", "<i4"), ("reserved", "<i4", (2,))]
 )
-assert CELL_DTYPE.itemsize == 48 and RESULT_DTYPE.itemsize == 64
+BNB_RESULT_DTYPE = np.dtype([("min_cost", "<f8"), ("n_evals", "<i4"), ("status", "<i4")])   # randt_bnb_result
+assert CELL_DTYPE.itemsize == 48 and RESULT_DTYPE.itemsize == 64 and BNB_RESULT_DTYPE.itemsize == 16
 
 PARAM_MANIFOLD, PARAM_AMBIENT4, PARAM_VECTOR, PARAM_ANALYTIC = 0, 1, 2, 3
 OK, ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM, ERR_NODEVICE = range(6)
@@ -72,6 +73,10 @@ class BnbParams(C.Structure):
     _fields_ = [("csm_window_linear", C.c_double), ("csm_window_angular", C.c_double), ("csm_linear_step", C.c_double),
                 ("csm_cost_threshold", C.c_double), ("csm_max_px_accurate_range", C.c_double), ("csm_n_iter", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class BnbResult(C.Structure):
+    _fields_ = [("min_cost", C.c_double), ("n_evals", C.c_int32), ("status", C.c_int32)]
 
 
 class PgParams(C.Structure):
@@ -148,9 +153,12 @@ SYMBOLS = {
     "randt_register_batch_dev": (_I, [_V, _V, _V, _V, _I, _I, _P(MatcherParams), _V, _V]),
     "randt_scan_register_batch_dev": (_I, [_V, _V, _I, _I, _V, _I, _I, _P(ClusterParams), _V, _V, _V, _P(MatcherParams), _V, _V]),
     "randt_register_pair": (_I, [_V, _V, _I, _V, _I, _P(MatcherParams), _V, _V]),
+    "randt_register_pairs": (_I, [_V, _V, _V, _V, _I, _I, _P(MatcherParams), _V, _V]),
     "randt_eval_cost_batch_dev": (_I, [_V, _V, _I, _V, _I, _V, _P(MatcherParams), C.c_double, _V, _I, _V, _V]),
     "randt_search_global": (_I, [_V, _V, _I, _V, _I, _P(MatcherParams), _P(BnbParams), C.c_double, C.c_double, C.c_double, _V,
                                  _P(C.c_double), _P(_I)]),
+    "randt_search_global_batch_dev": (_I, [_V, _V, _V, _V, _I, _I, _P(MatcherParams), _P(BnbParams), C.c_double, _V, _V, _I, _V, _V]),
+    "randt_search_global_batch": (_I, [_V, _V, _V, _V, _I, _I, _P(MatcherParams), _P(BnbParams), C.c_double, _V, _V, _I, _V, _V, _V]),
     "randt_cs_divergence_batch_dev": (_I, [_V, _V, _I, _I, _V, _V, _I, _I, _V, _V, _V]),
     "randt_cs_divergence": (_I, [_V, _V, _I, _V, _I, _V, _V, _V]),
     "randt_filter_scan_batch_dev": (_I, [_V, _V, _I, _I, _I, _I, _I, _P(FilterParams), _V, _I, _V, _V, _V, _V, _V]),

@@ -1393,6 +1393,28 @@ int randt_register_pair(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, 
   return RANDT_OK;
 }
 
+int randt_register_pairs(randt_ctx* ctx, const randt_maps* fixed, const int32_t* h_fixed_idx, const randt_maps* moving, int moving_first,
+                         int n_pairs, const randt_matcher_params* mp, double* h_pose4, randt_result* h_results) {
+  DeviceGuard dev_guard__(ctx);
+  if (!ctx || !fixed || !h_fixed_idx || !h_pose4 || !mp || n_pairs < 1 || !range_ok(moving, moving_first, n_pairs)) return RANDT_ERR_INVALID;
+  for (int p = 0; p < n_pairs; ++p)
+    if (!range_ok(fixed, h_fixed_idx[p], 1)) return RANDT_ERR_INVALID;
+  struct Layout { double* pose; randt_result* res; int32_t* idx; };
+  auto layout = [&](Carve& c) { return Layout{c.take<double>(4 * (size_t)n_pairs), c.take<randt_result>(n_pairs), c.take<int32_t>(n_pairs)}; };
+  PooledBlock blk(ctx);
+  RANDT_HIP_CHECK(ctx, blk.alloc(carved_size(layout)));
+  Carve c(blk.p);
+  const Layout L = layout(c);
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.pose, h_pose4, sizeof(double) * 4 * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.idx, h_fixed_idx, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+  const int rc = randt_register_batch_dev(ctx, fixed, L.idx, moving, moving_first, n_pairs, mp, L.pose, L.res);
+  if (rc) return drained(ctx, rc);
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_pose4, L.pose, sizeof(double) * 4 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+  if (h_results) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_results, L.res, sizeof(randt_result) * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  return RANDT_OK;
+}
+
 int randt_eval_cost_batch_dev(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, const randt_maps* moving, int moving_idx,
                               const int32_t* d_corr, const randt_matcher_params* mp, double scale, const double* d_poses4,
                               int n_poses, double* d_cost, int32_t* d_n_res) {
@@ -1826,6 +1848,176 @@ int randt_search_global(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, 
   memcpy(h_trans4, best, sizeof(best));  // trans = best_trans (identity if nothing qualified), :606
   if (min_cost_out) *min_cost_out = min_cost;
   if (n_evals) *n_evals = evals;
+  return RANDT_OK;
+}
+
+// the argument checks of randt_search_global apart from the windows, for the batch entry
+static bool bnb_params_ok(const randt_matcher_params* mp, const randt_bnb_params* bp, double scale) {
+  return isfinite(bp->csm_linear_step) && bp->csm_linear_step > 0.0 && isfinite(bp->csm_max_px_accurate_range) &&
+         bp->csm_max_px_accurate_range > 0.0 && bp->csm_n_iter >= 1 && bp->csm_n_iter <= 16 && isfinite(bp->csm_window_linear) &&
+         isfinite(bp->csm_window_angular) && isfinite(bp->csm_cost_threshold) && isfinite(scale) && scale > 0.0 &&
+         isfinite(mp->loss_alpha) && bp->csm_linear_step < 2.0 * bp->csm_max_px_accurate_range;
+}
+
+int randt_search_global_batch_dev(randt_ctx* ctx, const randt_maps* fixed, const int32_t* d_fixed_idx, const randt_maps* moving,
+                                  int moving_first, int n_pairs, const randt_matcher_params* mp, const randt_bnb_params* bp,
+                                  double scale, const double* h_wl, const double* h_wa, int max_nodes, double* d_trans4,
+                                  randt_bnb_result* d_results) {
+  DeviceGuard dev_guard__(ctx);
+  if (!ctx || !fixed || !mp || !bp || !d_fixed_idx || !h_wl || !h_wa || !d_trans4 || !d_results || n_pairs < 1 || max_nodes < 1 ||
+      !range_ok(moving, moving_first, n_pairs))
+    return RANDT_ERR_INVALID;
+  if (!bnb_params_ok(mp, bp, scale))
+    return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: steps / ranges must be finite and positive, csm_n_iter in 1..16", hipSuccess);
+  for (int p = 0; p < n_pairs; ++p)
+    if (!isfinite(h_wl[p]) || !isfinite(h_wa[p]))
+      return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: the search windows must be finite", hipSuccess);
+  if (n_pairs > 65535) return randt_set_error(ctx, RANDT_ERR_UNSUPPORTED, "correlative search: at most 65535 pairs per call", hipSuccess);
+  randt_note_user(ctx, fixed);
+  randt_note_user(ctx, moving);
+  const int k = 4;  // addNDTFactor(..., 4), :520
+  const int n_iter = bp->csm_n_iter;
+  const double linear_step = bp->csm_linear_step, max_range = bp->csm_max_px_accurate_range;
+  const double angular_step = acos(1 - ((linear_step * linear_step) / (2 * max_range * max_range)));
+  const double initial_linear_step = pow(2, (double)n_iter - 1) * linear_step;
+  // one level-1 delta table per distinct pair of windows (after the fmin of :505-506), in the order of the loops :527-541.  A
+  // grid larger than max_nodes is only counted: its pairs are flagged by the seed kernel.
+  struct Grid { double swl, swa; int first, n; };
+  std::vector<Grid> grids;
+  std::vector<double> tables;       // level-1 deltas, then the 27 children deltas of every level below the first
+  std::vector<int32_t> pair_table(2 * (size_t)n_pairs);
+  int level1_bound = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    const double swl = fmin(h_wl[p], bp->csm_window_linear), swa = fmin(h_wa[p], bp->csm_window_angular);
+    size_t g = 0;
+    while (g < grids.size() && !(grids[g].swl == swl && grids[g].swa == swa)) ++g;
+    if (g == grids.size()) {
+      Grid ng{swl, swa, (int)(tables.size() / 4), 0};
+      for (double tx = -swl / 2.0; tx <= swl / 2.0; tx += initial_linear_step)
+        for (double ty = -swl / 2.0; ty <= swl / 2.0; ty += initial_linear_step)
+          for (double a = -swa / 2.0; a < swa / 2.0; a += angular_step) {
+            if (ng.n < max_nodes) {
+              double d4[4];
+              bnb_pose(a, tx, ty, d4);
+              tables.insert(tables.end(), d4, d4 + 4);
+            }
+            if (++ng.n == INT32_MAX) return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: level-1 grid too large", hipSuccess);
+          }
+      if (ng.n > max_nodes) tables.resize(4 * (size_t)ng.first);
+      grids.push_back(ng);
+    }
+    pair_table[2 * (size_t)p] = grids[g].first;
+    pair_table[2 * (size_t)p + 1] = grids[g].n;
+    if (grids[g].n <= max_nodes && grids[g].n > level1_bound) level1_bound = grids[g].n;
+  }
+  const size_t level1_doubles = tables.size();
+  for (int level = 1; level < n_iter; ++level) {
+    const double cls = pow(2.0, (double)level) * linear_step, cas = angular_step;
+    int n = 0;
+    for (double tx = -cls; tx <= cls; tx += cls)
+      for (double ty = -cls; ty <= cls; ty += cls)
+        for (double a = -cas; a <= cas; a += cas, ++n) {
+          double d4[4];
+          bnb_pose(a, tx, ty, d4);
+          tables.insert(tables.end(), d4, d4 + 4);
+        }
+    if (n != 27) return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: a level's step grid is not 3 x 3 x 3", hipSuccess);
+  }
+  // The workspace is grow-only context memory of 60 B x n_pairs x max_nodes (keys 16, poses 32, costs 8, admitted 4) plus the
+  // correspondence tables: 7.5 MB for 64 pairs at max_nodes 2048, 250 MB for 512 pairs at the default 8192 -- callers with large
+  // batches and shallow searches pass a max_nodes that fits them (an overflowing pair is flagged, not wrong).
+  // [host image: tables | pair table] | correspondences | per-node keys, poses, costs, admitted | per-pair level, residuals, state
+  const size_t table_bytes = sizeof(double) * tables.size(), pt_bytes = sizeof(int32_t) * pair_table.size();
+  const size_t pt_at = (table_bytes + 255) & ~(size_t)255, image_bytes = pt_at + pt_bytes;
+  const size_t nodes = (size_t)n_pairs * max_nodes;
+  struct Layout { char* image; int32_t* corr; float* keys; double *poses, *cost; int32_t* admitted; int2* level; int32_t* n_res; BnbState* state; };
+  auto layout = [&](Carve& c) {
+    return Layout{c.take<char>(image_bytes), c.take<int32_t>((size_t)n_pairs * moving->v.cap * k), c.take<float>(4 * nodes),
+                  c.take<double>(4 * nodes), c.take<double>(nodes), c.take<int32_t>(nodes), c.take<int2>(n_pairs), c.take<int32_t>(n_pairs),
+                  c.take<BnbState>(n_pairs)};
+  };
+  int rc = randt_scratch_reserve(ctx, ctx->ws, carved_size(layout));
+  if (rc) return rc;
+  Carve c(ctx->ws.p);
+  const Layout L = layout(c);
+  const HostSpan spans[2] = {{tables.data(), table_bytes, 0}, {pair_table.data(), pt_bytes, pt_at}};
+  const void* d_image = nullptr;
+  bool must_sync = false;
+  rc = stage_host(ctx, spans, 2, image_bytes, true, &d_image, &must_sync);  // the image is the first thing carved
+  if (rc) return rc;
+  BnbBatch b{};
+  b.n_pairs = n_pairs; b.max_nodes = max_nodes; b.n_iter = n_iter; b.moving_first = moving_first; b.k = k;
+  b.level1_bound = level1_bound;
+  b.threshold = bp->csm_cost_threshold; b.scale = scale; b.alpha = mp->loss_alpha;
+  b.lookup_mahalanobis = mp->lookup_mahalanobis; b.use_intensity = mp->use_intensity;
+  b.fixed_idx = d_fixed_idx;
+  b.level1 = reinterpret_cast<const double*>(L.image);
+  b.children = b.level1 + level1_doubles;
+  b.pair_table = reinterpret_cast<const int2*>(L.image + pt_at);
+  b.corr = L.corr; b.keys = L.keys; b.poses = L.poses; b.cost = L.cost; b.admitted = L.admitted;
+  b.level = L.level; b.n_res = L.n_res; b.state = L.state;
+  b.trans4 = d_trans4; b.results = d_results;
+  ctx->bnb_last.poses_at = (size_t)(reinterpret_cast<char*>(L.poses) - static_cast<char*>(ctx->ws.p));
+  ctx->bnb_last.level_at = (size_t)(reinterpret_cast<char*>(L.level) - static_cast<char*>(ctx->ws.p));
+  ctx->bnb_last.n_pairs = n_pairs;
+  ctx->bnb_last.max_nodes = max_nodes;
+  return staged_tail(ctx, launch_search_global_batch(ctx, fixed->v, moving->v, b), must_sync);
+}
+
+// debug / test hook (not part of the ABI): the poses of every node `pair` generated in the context's last
+// randt_search_global_batch_dev, in FIFO order, as long as no other entry has used the workspace since (synchronises)
+int randt_debug_search_batch_nodes(randt_ctx* ctx, int pair, double* h_poses4, int max_out, int* n_nodes) {
+  DeviceGuard dev_guard__(ctx);
+  if (!ctx || !h_poses4 || !n_nodes || pair < 0 || pair >= ctx->bnb_last.n_pairs || !ctx->ws.p) return RANDT_ERR_INVALID;
+  const char* ws = static_cast<const char*>(ctx->ws.p);
+  int32_t level[2] = {0, 0};
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(level, ws + ctx->bnb_last.level_at + sizeof(level) * (size_t)pair, sizeof(level), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  const int n = level[0] + level[1];
+  if (n < 0 || n > ctx->bnb_last.max_nodes) return RANDT_ERR_INVALID;
+  *n_nodes = n;
+  const int take = n < max_out ? n : max_out;
+  if (take > 0) {
+    RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_poses4, ws + ctx->bnb_last.poses_at + sizeof(double) * 4 * (size_t)pair * ctx->bnb_last.max_nodes,
+                                        sizeof(double) * 4 * (size_t)take, hipMemcpyDeviceToHost, ctx->stream));
+    RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  }
+  return RANDT_OK;
+}
+
+int randt_search_global_batch(randt_ctx* ctx, const randt_maps* fixed, const int32_t* h_fixed_idx, const randt_maps* moving,
+                              int moving_first, int n_pairs, const randt_matcher_params* mp, const randt_bnb_params* bp, double scale,
+                              const double* h_wl, const double* h_wa, int max_nodes, double* h_trans4, double* h_min_cost,
+                              int32_t* h_n_evals) {
+  DeviceGuard dev_guard__(ctx);
+  if (!ctx || !fixed || !h_fixed_idx || !h_trans4 || !h_min_cost || n_pairs < 1) return RANDT_ERR_INVALID;
+  for (int p = 0; p < n_pairs; ++p)
+    if (!range_ok(fixed, h_fixed_idx[p], 1)) return RANDT_ERR_INVALID;
+  if (max_nodes <= 0) max_nodes = 8192;
+  struct Layout { double* trans4; randt_bnb_result* res; int32_t* idx; };
+  auto layout = [&](Carve& c) { return Layout{c.take<double>(4 * (size_t)n_pairs), c.take<randt_bnb_result>(n_pairs), c.take<int32_t>(n_pairs)}; };
+  PooledBlock blk(ctx);
+  RANDT_HIP_CHECK(ctx, blk.alloc(carved_size(layout)));
+  Carve c(blk.p);
+  const Layout L = layout(c);
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.trans4, h_trans4, sizeof(double) * 4 * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.idx, h_fixed_idx, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+  int rc = randt_search_global_batch_dev(ctx, fixed, L.idx, moving, moving_first, n_pairs, mp, bp, scale, h_wl, h_wa, max_nodes, L.trans4, L.res);
+  if (rc) return drained(ctx, rc);
+  std::vector<randt_bnb_result> res(n_pairs);
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_trans4, L.trans4, sizeof(double) * 4 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(res.data(), L.res, sizeof(randt_bnb_result) * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  for (int p = 0; p < n_pairs; ++p) {
+    int evals = res[p].n_evals;
+    h_min_cost[p] = res[p].min_cost;
+    if (res[p].status != 0) {  // its row still holds the guess
+      rc = randt_search_global(ctx, fixed, h_fixed_idx[p], moving, moving_first + p, mp, bp, scale, h_wl[p], h_wa[p], h_trans4 + 4 * (size_t)p,
+                               h_min_cost + p, &evals);
+      if (rc) return rc;
+    }
+    if (h_n_evals) h_n_evals[p] = evals;
+  }
   return RANDT_OK;
 }
 

@@ -130,6 +130,8 @@ struct randt_ctx {
   bool pin_pending[kPinSegs] = {false, false, false, false};
   randt_maps* tmp_cluster = nullptr;  // one-cell scratch map of randt_maps_insert_cluster (created once per context)
   size_t merge_lds_granted = 0;       // dynamic LDS k_maps_merge has been granted on this context's device (mapops.hip)
+  // where the last randt_search_global_batch_dev left its node poses / level ranges in `ws` (randt_debug_search_batch_nodes)
+  struct { size_t poses_at = 0, level_at = 0; int n_pairs = 0, max_nodes = 0; } bnb_last;
   hipEvent_t marker_ev = nullptr;     // "everything this context has enqueued so far", recorded when a batch ANOTHER context owns
                                       // and this one has used is destroyed (randt_maps_destroy waits for it on the owner's stream)
 };
@@ -291,3 +293,37 @@ int launch_cell_update(randt_ctx* ctx, randt_cell* d_cell, const float* d_pts, i
 int launch_eval_cost(randt_ctx* ctx, const MapView& fixed, int fmap, const MapView& moving, int mmap, const int32_t* d_corr, int k,
                      int use_intensity, double scale, double alpha, const double* d_poses4, int n_poses, double* d_cost,
                      int32_t* d_n_res);
+
+// bnb.hip: Matcher::estimateTransformGlobalBNB for n_pairs pairs at once, level loop on the device (randt_search_global_batch_dev)
+struct alignas(64) BnbState {
+  double min_cost, best[4];
+  int32_t n_evals, status;
+};
+struct BnbBatch {
+  // host-known
+  int n_pairs, max_nodes, n_iter, moving_first, k;
+  int level1_bound;  // the largest level-1 count of the batch
+  double threshold, scale, alpha;
+  int lookup_mahalanobis, use_intensity;
+  // device: inputs staged by the caller
+  const int32_t* fixed_idx;
+  const int2* pair_table;   // [n_pairs] (first entry, entries) of the pair's level-1 delta table
+  const double* level1;     // delta poses of the level-1 grids, 4 doubles each
+  const double* children;   // [n_iter - 1][27] delta poses of the levels below
+  // device: workspace
+  int32_t* corr;            // [n_pairs][moving.cap][k]
+  float* keys;              // [n_pairs][max_nodes] x 4 floats: every key generated so far = the nodes in FIFO order
+  double* poses;            // [n_pairs][max_nodes] x 4
+  double* cost;             // [n_pairs][max_nodes]
+  int32_t* admitted;        // [n_pairs][max_nodes]
+  int2* level;              // [n_pairs] (first node, nodes) of the level to evaluate
+  int32_t* n_res;           // [n_pairs]
+  BnbState* state;          // [n_pairs]
+  // in / out
+  double* trans4;
+  randt_bnb_result* results;
+};
+// debug / test hook, exported but not part of the ABI (include/randt.h does not declare it): the poses of every node `pair`
+// generated in the context's last randt_search_global_batch_dev, in FIFO order (tests/test_gpu_search_batch.py, T0)
+extern "C" int randt_debug_search_batch_nodes(randt_ctx* ctx, int pair, double* h_poses4, int max_out, int* n_nodes);
+int launch_search_global_batch(randt_ctx* ctx, const MapView& fixed, const MapView& moving, const BnbBatch& b);

@@ -699,6 +699,38 @@ def search_global(ctx, fixed, fixed_idx, moving, moving_idx, mp, bp, trans4, sca
     return mc.value, t, ne.value
 
 
+def _windows(window_linear, window_angular, n_pairs):
+    wl = np.ascontiguousarray(np.broadcast_to(np.asarray(window_linear, dtype=np.float64), (n_pairs,)))
+    wa = np.ascontiguousarray(np.broadcast_to(np.asarray(window_angular, dtype=np.float64), (n_pairs,)))
+    return wl, wa
+
+
+def search_global_batch_dev(ctx, fixed, fixed_idx, moving, moving_first, n_pairs, mp, bp, trans4, results, scale=1.5, window_linear=4.5,
+                            window_angular=0.45, max_nodes=8192):
+    """randt_search_global_batch_dev: the search of search_global for n_pairs pairs, enqueued only.  fixed_idx (int32), trans4
+    (n_pairs, 4) float64 in: guesses / out: best poses, results (n_pairs,) BNB_RESULT_DTYPE bytes: device tensors; the windows
+    are host scalars or arrays of n_pairs."""
+    wl, wa = _windows(window_linear, window_angular, n_pairs)
+    ctx._check(ctx._lib.randt_search_global_batch_dev(ctx._h, fixed._h, _dptr(fixed_idx), moving._h, int(moving_first), int(n_pairs), C.byref(mp),
+                                                      C.byref(bp), float(scale), wl.ctypes.data, wa.ctypes.data, int(max_nodes), _dptr(trans4),
+                                                      _dptr(results)), "randt_search_global_batch_dev")
+
+
+def search_global_batch(ctx, fixed, fixed_idx, moving, moving_first, mp, bp, trans4, scale=1.5, window_linear=4.5, window_angular=0.45,
+                        max_nodes=0):
+    """randt_search_global_batch (synchronous): host arrays, pair p = moving map moving_first + p against fixed map fixed_idx[p].
+    Returns (min_cost [n], pose4 [n][4], n_evals [n]) -- search_global's answers, whatever max_nodes (0 = the default) is."""
+    t = np.array(trans4, dtype=np.float64).reshape(-1, 4)
+    n = len(t)
+    fi = np.ascontiguousarray(fixed_idx, dtype=np.int32).reshape(n)
+    wl, wa = _windows(window_linear, window_angular, n)
+    mc, ne = np.zeros(n), np.zeros(n, dtype=np.int32)
+    ctx._check(ctx._lib.randt_search_global_batch(ctx._h, fixed._h, fi.ctypes.data, moving._h, int(moving_first), n, C.byref(mp), C.byref(bp),
+                                                  float(scale), wl.ctypes.data, wa.ctypes.data, int(max_nodes), t.ctypes.data, mc.ctypes.data,
+                                                  ne.ctypes.data), "randt_search_global_batch")
+    return mc, t, ne
+
+
 # ------------------------------------------------------------------ multi-GPU group (SURVEY 8(e)) ----
 def shard_range(n_items, world, rank):
     """randt_shard_range: contiguous split, remainders to the low ranks."""

@@ -37,7 +37,9 @@ class HipBackend:
 
         self.torch = torch
         self.ctx, self.mapp, self.clu = ctx, map_params, cluster_params
+        self.scan_capacity = scan_capacity
         self.scans = host.Maps(ctx, scan_slots, map_params, scan_capacity, with_grid=False)
+        self._stage = None          # contiguous copies of the scans of a candidate batch (loop_candidates_batch)
         self.subs = host.Maps(ctx, submap_slots, map_params, map_params.size_x * map_params.size_y, with_grid=True)
         self.free_scans = list(range(scan_slots))
         self.free_subs = list(range(submap_slots))
@@ -152,6 +154,56 @@ class HipBackend:
         bp = host.bnb_params() if bp is None else bp
         _, p, _ = host.search_global(self.ctx, self.subs, sub_idx, self.scans, scan_idx, mp, bp, guess4, scale, window_linear, window_angular)
         return p
+
+    def _stage_scans(self, scan_idx):
+        """The batch entries take the moving maps moving_first .. moving_first + n - 1: copies of the candidates' scans."""
+        n = len(scan_idx)
+        if self._stage is None or self._stage.n_maps < n:
+            if self._stage is not None:
+                self._stage.close()
+            self._stage = host.Maps(self.ctx, max(8, 2 * n), self.mapp, self.scan_capacity, with_grid=False)
+        for p, s in enumerate(scan_idx):
+            self._stage.copy_from(self.scans, dst_first=p, src_first=int(s), count=1)
+        return self._stage
+
+    def search_global_batch(self, sub_idx, scan_idx, mp, bp, guess4, scale, window_linear, window_angular):
+        """search_global for many (submap, scan) pairs in one device batch; returns the best poses [n][4]."""
+        bp = host.bnb_params() if bp is None else bp
+        _, p, _ = host.search_global_batch(self.ctx, self.subs, sub_idx, self._stage_scans(scan_idx), 0, mp, bp, guess4, scale,
+                                           window_linear, window_angular)
+        return p
+
+    def loop_candidates_batch(self, sub_idx, scan_idx, guess4, loop_mp, search=None):
+        """search_global (if search = (mp, bp, scale, windows_linear, windows_angular)) -> register_pair -> cs_divergence for n
+        candidates as three device batches on one stream, nothing read in between; returns (poses [n][4], cs [n])."""
+        torch = self.torch
+        n = len(sub_idx)
+        stage = self._stage_scans(scan_idx)
+        sizes = (32 * n, 8 * n, 16 * n, 64 * n, 4 * n)      # poses | cs | search results | registration results | fixed indices
+        offs = np.concatenate([[0], np.cumsum([(b + 255) // 256 * 256 for b in sizes])])
+        h_buf = np.zeros(int(offs[-1]), dtype=np.uint8)
+        h_buf[offs[0]:offs[0] + sizes[0]] = np.ascontiguousarray(guess4, dtype=np.float64).reshape(n, 4).view(np.uint8).reshape(-1)
+        h_buf[offs[4]:offs[4] + sizes[4]] = np.asarray(sub_idx, dtype=np.int32).view(np.uint8)
+        buf = torch.from_numpy(h_buf).to(self.dev)
+        pose, cs, bres, rres, fidx = (buf[int(offs[i]):int(offs[i]) + sizes[i]] for i in range(5))
+        if search is not None:
+            mp, bp, scale, wl, wa = search
+            host.search_global_batch_dev(self.ctx, self.subs, fidx, stage, 0, n, mp, host.bnb_params() if bp is None else bp, pose, bres,
+                                         scale, wl, wa)
+        host.register_batch(self.ctx, self.subs, fidx, stage, 0, n, loop_mp, pose, rres)
+        lo, hi = int(min(sub_idx)), int(max(sub_idx))
+        host.cs_divergence_batch(self.ctx, self.subs, lo, hi - lo + 1, fidx, stage, 0, n, pose, cs)
+        self.ctx.synchronize()
+        h = buf.cpu().numpy()
+        est = h[offs[0]:offs[0] + sizes[0]].view(np.float64).reshape(n, 4).copy()
+        out_cs = h[offs[1]:offs[1] + sizes[1]].view(np.float64).copy()
+        if search is not None:
+            status = h[offs[2]:offs[2] + sizes[2]].view(host._capi.BNB_RESULT_DTYPE)["status"]
+            for p in np.nonzero(status)[0]:              # more nodes than the batch's bound: this candidate goes the single way
+                g = self.search_global(sub_idx[p], scan_idx[p], search[0], search[1], guess4[p], search[2], search[3][p], search[4][p])
+                est[p], _ = self.register_pair(sub_idx[p], scan_idx[p], loop_mp, g)
+                out_cs[p] = self.cs_divergence(sub_idx[p], scan_idx[p], est[p])
+        return est, out_cs
 
     def register_window(self, fixed_idx, moving_idx, states, mp, wp, trans4, imu=None):
         st, t, rej, res = host.register_window(self.ctx, self.subs, fixed_idx, self.scans, moving_idx, states, mp, wp, trans4, imu)

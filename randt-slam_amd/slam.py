@@ -46,11 +46,15 @@ class Slam(Odometry):
     def __init__(self, backend, matcher_params, window_params, loop_matcher_params, params=None, sc_params=None,
                  loop_closure_max_cs_divergence=3.6, loop_closure_weight=4.0e4, loop_sqrtI=None, pg_params=None,
                  loop_search="scan_context", max_data_association_mahalanobis_dist=0.5, compute_dfs_loop_closure=False,
-                 bnb_params=None, bnb_matcher_params=None, loop_closure_scale=1.5):
+                 bnb_params=None, bnb_matcher_params=None, loop_closure_scale=1.5, batch_loop_search=False):
         super().__init__(backend, matcher_params, window_params, params)
         if loop_search not in ("scan_context", "covariance"):
             raise ValueError("loop_search must be 'scan_context' or 'covariance'")
         self.loop_search = loop_search
+        # covariance mode: the candidates of all pending queries as ONE device batch (a backend without loop_candidates_batch
+        # runs them one by one)
+        self.batch_loop_search = bool(batch_loop_search)
+        self.loop_batches = []         # covariance mode: candidates per detect_loop_closures call
         self.max_mahalanobis = float(max_data_association_mahalanobis_dist)   # base yaml :26
         self.compute_dfs = bool(compute_dfs_loop_closure)                     # base yaml :25
         self.bnb_params = bnb_params                                          # csm_* of the matcher (backend default if None)
@@ -131,41 +135,74 @@ class Slam(Odometry):
         return added
 
     # ---- LocalFuser::detectLoopClosures, the branch without Scan Context (:351-412), quirks included -------
-    def _detect_loop_closures_covariance(self):
-        added = 0
+    def _covariance_candidates(self, q):
+        """The candidates of query node q: per finished submap within the gate its closest node, in std::map order, as
+        (q, candidate node, submap, guess, search windows or None)."""
         thr = self.max_mahalanobis
+        best = {}                                  # submap -> (node, dist): the closest node of every finished submap
+        tq = self.nodes[q]
+        for i in range(len(self.nodes)):
+            sub_i = self.submap_idzs[i]
+            if sub_i == self.submap_idzs[q] or sub_i == self.n_finished_submaps or sub_i not in self.submaps:   # :355
+                continue
+            dist = _mahalanobis2(self.node_cov[i], tq[2] - self.nodes[i][2], tq[3] - self.nodes[i][3])           # :357, the NODE's covariance
+            if dist is None:                       # never covered by an optimisation (the reference: NaN < thr is false)
+                continue
+            if dist < thr and (sub_i not in best or dist < best[sub_i][1]):                                     # :358-362
+                best[sub_i] = (i, dist)
+        out = []
+        for sub_i in sorted(best):                 # std::map order
+            lid = best[sub_i][0]
+            root = self.nodes[self.root_nodes[sub_i]]
+            guess = _se2_mul4(_se2_inv4(root), tq)                                                              # :376
+            windows = None
+            if self.compute_dfs:                                                                                # :379-388
+                cov = self.node_cov[lid]
+                lam0 = _smaller_eigenvalue2(cov)   # eigenvalues()(0): the SMALLER one, named "max" there, no root taken
+                windows = (thr * abs(lam0), min(2 * math.pi, thr * math.sqrt(cov[2, 2])))
+            out.append((q, lid, sub_i, guess, windows))
+        return out
+
+    def _close_loop(self, q, lid, sub_i, est, cs):
+        ok = bool(cs < self.max_cs)
+        self.loop_log.append((q, lid, float(cs), ok))
+        if ok:
+            self.edges.append((self.root_nodes[sub_i], q, np.array(est, dtype=np.float64), self.loop_sqrt_info))   # :402-409
+        return int(ok)
+
+    def _detect_loop_closures_covariance(self):
+        if self.batch_loop_search and hasattr(self.b, "loop_candidates_batch"):
+            return self._detect_loop_closures_covariance_batched()
+        added = n_cands = 0
         while self.pending_loop_search:
             q = self.pending_loop_search.pop(0)
-            best = {}                                  # submap -> (node, dist): the closest node of every finished submap
-            tq = self.nodes[q]
-            for i in range(len(self.nodes)):
-                sub_i = self.submap_idzs[i]
-                if sub_i == self.submap_idzs[q] or sub_i == self.n_finished_submaps or sub_i not in self.submaps:   # :355
-                    continue
-                dist = _mahalanobis2(self.node_cov[i], tq[2] - self.nodes[i][2], tq[3] - self.nodes[i][3])           # :357, the NODE's covariance
-                if dist is None:                       # never covered by an optimisation (the reference: NaN < thr is false)
-                    continue
-                if dist < thr and (sub_i not in best or dist < best[sub_i][1]):                                     # :358-362
-                    best[sub_i] = (i, dist)
-            for sub_i in sorted(best):                 # std::map order
-                lid = best[sub_i][0]
-                root = self.nodes[self.root_nodes[sub_i]]
-                guess = _se2_mul4(_se2_inv4(root), tq)                                                              # :376
-                if self.compute_dfs:                                                                                # :379-388
-                    cov = self.node_cov[lid]
-                    lam0 = _smaller_eigenvalue2(cov)   # eigenvalues()(0): the SMALLER one, named "max" there, no root taken
-                    window_linear = thr * abs(lam0)
-                    window_angular = min(2 * math.pi, thr * math.sqrt(cov[2, 2]))
+            for _, lid, sub_i, guess, windows in self._covariance_candidates(q):
+                n_cands += 1
+                if windows is not None:
                     guess = self.b.search_global(self.submaps[sub_i], self.node_scans[q], self.bnb_mp, self.bnb_params, guess,
-                                                 self.loop_scale, window_linear, window_angular)
+                                                 self.loop_scale, windows[0], windows[1])
                 est, _cost = self.b.register_pair(self.submaps[sub_i], self.node_scans[q], self.loop_mp, guess)     # :395
                 cs = self.b.cs_divergence(self.submaps[sub_i], self.node_scans[q], est)                             # :396-397
-                ok = bool(cs < self.max_cs)
-                self.loop_log.append((q, lid, float(cs), ok))
-                if ok:
-                    self.edges.append((self.root_nodes[sub_i], q, np.array(est, dtype=np.float64), self.loop_sqrt_info))   # :402-409
-                    added += 1
+                added += self._close_loop(q, lid, sub_i, est, cs)
+        self.loop_batches.append(n_cands)
         return added
+
+    def _detect_loop_closures_covariance_batched(self):
+        """The same search with the candidates of every pending query in one batch (they do not depend on each other: nodes and
+        covariances only change in optimize_pose_graph): one batched global search, one batched refinement, one batched CS
+        gate on the device, one read-back; log and edges in the sequential order."""
+        cands = []
+        while self.pending_loop_search:
+            cands += self._covariance_candidates(self.pending_loop_search.pop(0))
+        self.loop_batches.append(len(cands))
+        if not cands:
+            return 0
+        search = None
+        if self.compute_dfs:
+            search = (self.bnb_mp, self.bnb_params, self.loop_scale, [c[4][0] for c in cands], [c[4][1] for c in cands])
+        est, cs = self.b.loop_candidates_batch([self.submaps[c[2]] for c in cands], [self.node_scans[c[0]] for c in cands],
+                                               np.array([c[3] for c in cands]), self.loop_mp, search)
+        return sum(self._close_loop(c[0], c[1], c[2], est[p], cs[p]) for p, c in enumerate(cands))
 
     # ---- NDTSlam::optimizePoseGraph (ndt_slam.cpp:351-361) --------------------------------------
     def optimize_pose_graph(self):
