@@ -759,28 +759,18 @@ class Matcher {
     std::vector<double> cost(static_cast<size_t>(n_pairs), failed_value());
     randt_group* g = group.get();
     randt_matcher_params mp;
-    if (!g || n_pairs == 0 || n_fixed == 0 || static_cast<int>(trans.size()) != n_pairs || static_cast<int>(fixed_of_pair.size()) != n_pairs) {
-      facade_check(RANDT_ERR_INVALID, "estimateLoopConstraintBatch: group / argument sizes", nullptr);
+    const char* what = "estimateLoopConstraintBatch: group / argument sizes";
+    if (!g) {
+      facade_check(RANDT_ERR_INVALID, what, nullptr);
       return cost;
     }
+    if (!check_pairs(trans, fixed_ndts, fixed_of_pair, moving_ndts, what, "estimateLoopConstraintBatch")) return cost;
     if (!loop_params(max_gnc_steps, use_intensity_as_dimension, scale, &mp, randt_group_ctx(g, 0))) return cost;
     int world = 0, n_local = 0;
     randt_group_info(g, &world, &n_local, nullptr, nullptr);
     int fcap = 1, mcap = 1;
     for (const Map* m : fixed_ndts) fcap = std::max(fcap, m->capacity());
     for (const Map* m : moving_ndts) mcap = std::max(mcap, m->capacity());
-    // one parameter set per batch (the reference has one, with a zero centre): differently centred or scaled maps would be
-    // associated in the wrong geometry without an error
-    for (const Map* m : fixed_ndts)
-      if (std::memcmp(&m->params(), &fixed_ndts[0]->params(), sizeof(randt_map_params)) != 0) {
-        facade_check(RANDT_ERR_INVALID, "estimateLoopConstraintBatch: the fixed maps must share one geometry (centre, resolution, window)", nullptr);
-        return cost;
-      }
-    for (const Map* m : moving_ndts)
-      if (std::memcmp(&m->params(), &moving_ndts[0]->params(), sizeof(randt_map_params)) != 0) {
-        facade_check(RANDT_ERR_INVALID, "estimateLoopConstraintBatch: the moving maps must share one geometry", nullptr);
-        return cost;
-      }
     std::vector<randt_maps*> fb(static_cast<size_t>(n_local), nullptr), mb(static_cast<size_t>(n_local), nullptr);
     auto cleanup = [&] {
       randt_group_synchronize(g);
@@ -814,13 +804,7 @@ class Matcher {
       cleanup();
       return cost;
     }
-    for (int p = 0; p < n_pairs; ++p) {
-      if (res[p].n_residuals == 0) {
-        std::cout << "WARNING: NO RESIDUALS ADDED!" << std::endl;  // pose untouched, like the single call
-      }
-      std::copy(pose.begin() + 4 * p, pose.begin() + 4 * p + 4, trans[p].d);
-      cost[p] = res[p].cost;
-    }
+    write_back(pose, res, trans, cost);
     if (stats) *stats = res;
     cleanup();
     last_status() = RANDT_OK;
@@ -841,11 +825,7 @@ class Matcher {
     std::vector<randt_result> res(static_cast<size_t>(n_pairs));
     const int rc = randt_register_pairs(b.ctx, b.fixed, b.fidx.data(), b.moving, 0, n_pairs, &mp, b.pose.data(), res.data());
     if (!facade_check(rc, "randt_register_pairs", b.ctx)) return cost;
-    for (int p = 0; p < n_pairs; ++p) {
-      if (res[p].n_residuals == 0) std::cout << "WARNING: NO RESIDUALS ADDED!" << std::endl;  // pose untouched, like the single call
-      std::copy(b.pose.begin() + 4 * p, b.pose.begin() + 4 * p + 4, trans[p].d);
-      cost[p] = res[p].cost;
-    }
+    write_back(b.pose, res, trans, cost);
     return cost;
   }
 
@@ -864,18 +844,8 @@ class Matcher {
       return cost;
     }
     if (!stage_pairs(trans, fixed_ndts, fixed_of_pair, moving_ndts, "estimateTransformGlobalBNBBatch", &b)) return cost;
-    randt_bnb_params csm{};
-    csm.csm_window_linear = parameters_.csm_window_linear;
-    csm.csm_window_angular = parameters_.csm_window_angular;
-    csm.csm_linear_step = parameters_.csm_linear_step;
-    csm.csm_cost_threshold = parameters_.csm_cost_threshold;
-    csm.csm_max_px_accurate_range = parameters_.csm_max_px_accurate_range;
-    csm.csm_n_iter = parameters_.csm_n_iter;
-    randt_matcher_params mp;
-    randt_matcher_params_default(&mp);
-    mp.loss_alpha = parameters_.loss_function_convexity;
-    mp.lookup_mahalanobis = parameters_.lookup_mahalanobis ? 1 : 0;
-    mp.use_intensity = use_intensity_as_dimension ? 1 : 0;
+    const randt_bnb_params csm = csm_params();
+    const randt_matcher_params mp = search_params(use_intensity_as_dimension);
     std::vector<double> min_cost(static_cast<size_t>(n_pairs));
     const int rc = randt_search_global_batch(b.ctx, b.fixed, b.fidx.data(), b.moving, 0, n_pairs, &mp, &csm, scale, windows_linear.data(),
                                              windows_angular.data(), 0, b.pose.data(), min_cost.data(), nullptr);
@@ -890,25 +860,14 @@ class Matcher {
   // The csm_* members come from the parameters given to initialize(), like in the reference.
   double estimateTransformGlobalBNB(SE2d& trans, const Map& fixed_ndt, Map& moving_ndt, bool use_intensity_as_dimension, double scale,
                                     double search_window_size_linear, double search_window_size_angular) const {
-    randt_bnb_params csm{};
-    csm.csm_window_linear = parameters_.csm_window_linear;
-    csm.csm_window_angular = parameters_.csm_window_angular;
-    csm.csm_linear_step = parameters_.csm_linear_step;
-    csm.csm_cost_threshold = parameters_.csm_cost_threshold;
-    csm.csm_max_px_accurate_range = parameters_.csm_max_px_accurate_range;
-    csm.csm_n_iter = parameters_.csm_n_iter;
     return estimateTransformGlobalBNB(trans, fixed_ndt, moving_ndt, use_intensity_as_dimension, scale, search_window_size_linear,
-                                      search_window_size_angular, csm);
+                                      search_window_size_angular, csm_params());
   }
   // the same with explicit csm_* values (not a reference signature)
   double estimateTransformGlobalBNB(SE2d& trans, const Map& fixed_ndt, Map& moving_ndt, bool use_intensity_as_dimension, double scale,
                                     double search_window_size_linear, double search_window_size_angular,
                                     const randt_bnb_params& csm) const {
-    randt_matcher_params mp;
-    randt_matcher_params_default(&mp);
-    mp.loss_alpha = parameters_.loss_function_convexity;
-    mp.lookup_mahalanobis = parameters_.lookup_mahalanobis ? 1 : 0;
-    mp.use_intensity = use_intensity_as_dimension ? 1 : 0;
+    const randt_matcher_params mp = search_params(use_intensity_as_dimension);
     double min_cost = 0.0;
     const int rc = randt_search_global(fixed_ndt.context()->get(), fixed_ndt.handle(), 0, moving_ndt.handle(), 0, &mp, &csm, scale,
                                        search_window_size_linear, search_window_size_angular, trans.data(), &min_cost, nullptr);
@@ -1072,6 +1031,51 @@ class Matcher {
     mp->parameterization = analytic() ? RANDT_PARAM_ANALYTIC : (parameters_.optimize_on_manifold ? RANDT_PARAM_AMBIENT4 : RANDT_PARAM_VECTOR);
     return true;
   }
+  // the csm_* members of the parameters given to initialize(), for the correlative search
+  randt_bnb_params csm_params() const {
+    randt_bnb_params csm{};
+    csm.csm_window_linear = parameters_.csm_window_linear;
+    csm.csm_window_angular = parameters_.csm_window_angular;
+    csm.csm_linear_step = parameters_.csm_linear_step;
+    csm.csm_cost_threshold = parameters_.csm_cost_threshold;
+    csm.csm_max_px_accurate_range = parameters_.csm_max_px_accurate_range;
+    csm.csm_n_iter = parameters_.csm_n_iter;
+    return csm;
+  }
+  // what the correlative search reads of randt_matcher_params (its cost is one evaluation, no solve)
+  randt_matcher_params search_params(bool use_intensity_as_dimension) const {
+    randt_matcher_params mp;
+    randt_matcher_params_default(&mp);
+    mp.loss_alpha = parameters_.loss_function_convexity;
+    mp.lookup_mahalanobis = parameters_.lookup_mahalanobis ? 1 : 0;
+    mp.use_intensity = use_intensity_as_dimension ? 1 : 0;
+    return mp;
+  }
+  // The arguments of a batch of pairs: one trans and one fixed_of_pair per moving map, every fixed_of_pair a valid index, and
+  // one parameter set per side (the reference has one, with a zero centre): differently centred or scaled maps would be
+  // associated in the wrong geometry without an error.  `what` names a size / index failure, `who` the geometry ones.
+  static bool check_pairs(const std::vector<SE2d>& trans, const std::vector<const Map*>& fixed_ndts, const std::vector<int>& fixed_of_pair,
+                          const std::vector<const Map*>& moving_ndts, const char* what, const char* who) {
+    const int n_pairs = static_cast<int>(moving_ndts.size()), n_fixed = static_cast<int>(fixed_ndts.size());
+    bool ok = n_pairs != 0 && n_fixed != 0 && static_cast<int>(trans.size()) == n_pairs && static_cast<int>(fixed_of_pair.size()) == n_pairs;
+    for (int f : fixed_of_pair) ok = ok && f >= 0 && f < n_fixed;
+    if (!ok) return facade_check(RANDT_ERR_INVALID, what, nullptr);
+    for (const Map* m : fixed_ndts)
+      if (std::memcmp(&m->params(), &fixed_ndts[0]->params(), sizeof(randt_map_params)) != 0)
+        return facade_check(RANDT_ERR_INVALID, (std::string(who) + ": the fixed maps must share one geometry (centre, resolution, window)").c_str(), nullptr);
+    for (const Map* m : moving_ndts)
+      if (std::memcmp(&m->params(), &moving_ndts[0]->params(), sizeof(randt_map_params)) != 0)
+        return facade_check(RANDT_ERR_INVALID, (std::string(who) + ": the moving maps must share one geometry").c_str(), nullptr);
+    return true;
+  }
+  // the results of a batched registration into the caller's vectors, with the single call's warning
+  static void write_back(const std::vector<double>& pose, const std::vector<randt_result>& res, std::vector<SE2d>& trans, std::vector<double>& cost) {
+    for (size_t p = 0; p < res.size(); ++p) {
+      if (res[p].n_residuals == 0) std::cout << "WARNING: NO RESIDUALS ADDED!" << std::endl;  // pose untouched, like the single call
+      std::copy(pose.begin() + 4 * p, pose.begin() + 4 * p + 4, trans[p].d);
+      cost[p] = res[p].cost;
+    }
+  }
   using StageKey = std::pair<std::uint64_t, std::uint64_t>;  // (Map::storage_id, Map::storage_version) of what a staging slot holds
   static int place_in_stage(randt_maps* batch, std::vector<StageKey>& keys, const std::vector<const Map*>& need, std::vector<int32_t>& slots) {
     slots.assign(need.size(), -1);
@@ -1146,28 +1150,10 @@ class Matcher {
   bool stage_pairs(const std::vector<SE2d>& trans, const std::vector<const Map*>& fixed_ndts, const std::vector<int>& fixed_of_pair,
                    const std::vector<const Map*>& moving_ndts, const char* what, PairBatches* b) const {
     const int n_pairs = static_cast<int>(moving_ndts.size()), n_fixed = static_cast<int>(fixed_ndts.size());
-    if (n_pairs == 0 || n_fixed == 0 || static_cast<int>(trans.size()) != n_pairs || static_cast<int>(fixed_of_pair.size()) != n_pairs) {
-      facade_check(RANDT_ERR_INVALID, what, nullptr);
-      return false;
-    }
-    for (int f : fixed_of_pair)
-      if (f < 0 || f >= n_fixed) {
-        facade_check(RANDT_ERR_INVALID, what, nullptr);
-        return false;
-      }
+    if (!check_pairs(trans, fixed_ndts, fixed_of_pair, moving_ndts, what, "batch")) return false;
     int fcap = 1, mcap = 1;
     for (const Map* m : fixed_ndts) fcap = std::max(fcap, m->capacity());
     for (const Map* m : moving_ndts) mcap = std::max(mcap, m->capacity());
-    for (const Map* m : fixed_ndts)
-      if (std::memcmp(&m->params(), &fixed_ndts[0]->params(), sizeof(randt_map_params)) != 0) {
-        facade_check(RANDT_ERR_INVALID, "batch: the fixed maps must share one geometry (centre, resolution, window)", nullptr);
-        return false;
-      }
-    for (const Map* m : moving_ndts)
-      if (std::memcmp(&m->params(), &moving_ndts[0]->params(), sizeof(randt_map_params)) != 0) {
-        facade_check(RANDT_ERR_INVALID, "batch: the moving maps must share one geometry", nullptr);
-        return false;
-      }
     b->ctx = fixed_ndts[0]->context()->get();
     int rc = randt_maps_create(b->ctx, n_fixed, &fixed_ndts[0]->params(), fcap, 1, &b->fixed);
     if (!rc) rc = randt_maps_create(b->ctx, n_pairs, &moving_ndts[0]->params(), mcap, 0, &b->moving);

@@ -110,63 +110,145 @@ class LocalFuser {
   const std::vector<LoopLog>& loopLog() const { return loop_log_; }
   const std::vector<Constraint>& edges() const { return edges_; }
 
-  // LocalFuser::detectLoopClosures, the branch without Scan Context (local_fuser.cpp:351-412), quirks included: per finished submap
-  // the node closest to the query in Mahalanobis distance under the NODE's cov_pos_pos (:357, "mathematically incorrect for
-  // manifold" there), optionally estimateTransformGlobalBNB with a window sized from the node's covariance (:380-387), then the
-  // refinement and the CS gate of the other branch.  A node whose cov_pos_pos is not positive definite (never covered by an
-  // optimisation: zeros) is skipped -- there the inverse of a zero matrix gives NaN and `NaN < thr` is false.
+  // ---- loop closure: LocalFuser::detectLoopClosures (local_fuser.cpp:318-416) ---------------------------------------------------
+  // The four public methods below are compositions of these helpers, each of which mirrors its reference lines ONCE:
+  //   scanContextCandidate   :323-333  the Scan Context query, its skips and the guess of :333
+  //   covarianceCandidates   :355-388  the Mahalanobis gate, the best node per submap, the guess of :376, the windows of :379-388
+  //   registerAndClose       :329-339 / :370-397  one candidate the reference's way: maps by value, search, registration, CS
+  //   closeLoop              :340-347 / :402-409  the CS gate, the log entry and the loop edge
+  //   stageCandidates, gateBatch       not in the reference: the lists of a batched registration and the gates behind it
+ private:
+  struct LoopCandidate {
+    int q, lid, sub_i;   // query node, candidate node, the candidate's (finished) submap
+    SE2d guess;
+    double window_linear, window_angular;   // of estimateTransformGlobalBNB (covariance branch with compute_dfs_loop_closure)
+  };
+
+  // the Scan Context branch (:322-333); false: no candidate for q
+  bool scanContextCandidate(int q, LoopCandidate* out) {
+    const std::pair<int, float> det = sc_manager_.detectLoopClosureID(q);   // :323
+    const int lid = det.first;
+    if (lid == -1 || submap_idzs_.at(q) == submap_idzs_.at(lid)) return false;
+    const int sub_i = submap_idzs_.at(lid);
+    if (!submaps_.count(sub_i)) return false;  // submaps_.at() would throw: the candidate's submap is still being built
+    const SE2d root = nodes_.at(root_nodes_.at(sub_i)).pose;
+    *out = {q, lid, sub_i, se2_mul(se2_mul(se2_inv(root), nodes_.at(lid).pose), SE2d(-static_cast<double>(det.second), 0.0, 0.0)), 0.0, 0.0};   // :333
+    return true;
+  }
+
+  // the branch without Scan Context (:351-412), quirks included: per finished submap the node closest to the query in Mahalanobis
+  // distance under the NODE's cov_pos_pos (:357, "mathematically incorrect for manifold" there), in std::map order, with the
+  // window estimateTransformGlobalBNB gets from the node's covariance (:380-387).  A node whose cov_pos_pos is not positive
+  // definite (never covered by an optimisation: zeros) is skipped -- there the inverse of a zero matrix gives NaN and
+  // `NaN < thr` is false.
+  void covarianceCandidates(int q, std::vector<LoopCandidate>& out) const {
+    const double thr = parameters_.max_data_association_mahalanobis_dist;
+    std::map<int, std::pair<int, double>> best_submap_matches;
+    const Pose& pq = nodes_.at(q);
+    for (const auto& pose_i : nodes_) {
+      const int sub_i = submap_idzs_.at(pose_i.first);
+      if (sub_i == submap_idzs_.at(q) || sub_i == n_finished_submaps_ || !submaps_.count(sub_i)) continue;   // :355
+      const std::array<double, 4>& P = pose_i.second.cov_pos_pos;
+      const double a = P[0], b = P[1], c = P[2], d = P[3], det = a * d - b * c;
+      if (!(a > 0.0 && det > 0.0)) continue;
+      const double dx = pq.pose.d[2] - pose_i.second.pose.d[2], dy = pq.pose.d[3] - pose_i.second.pose.d[3];
+      const double dist = std::sqrt((d * dx * dx - (b + c) * dx * dy + a * dy * dy) / det);                 // :357
+      if (dist < thr) {                                                                                     // :358-362
+        auto it = best_submap_matches.find(sub_i);
+        if (it == best_submap_matches.end() || dist < it->second.second) best_submap_matches[sub_i] = std::make_pair(pose_i.first, dist);
+      }
+    }
+    for (const auto& match : best_submap_matches) {
+      const int sub_i = match.first, lid = match.second.first;
+      const std::array<double, 9>& cov = nodes_.at(lid).cov;                                // :379-388
+      const double ca = cov[0], cc = cov[3], cd = cov[4];   // self-adjoint xy block, lower triangle read like Eigen does
+      const double lam0 = 0.5 * (ca + cd) - std::sqrt(0.25 * (ca - cd) * (ca - cd) + cc * cc);   // eigenvalues()(0): the SMALLER one
+      const double search_window_linear = thr * std::abs(lam0);   // named "max" there, and no root is taken: kept
+      const double search_window_angular = std::min(2 * M_PI, thr * std::sqrt(cov[8]));
+      out.push_back({q, lid, sub_i, se2_mul(se2_inv(nodes_.at(root_nodes_.at(sub_i)).pose), pq.pose) /* :376 */, search_window_linear,
+                     search_window_angular});
+    }
+  }
+
+  // the CS gate, the log entry and, if accepted, the loop edge (:340-347, :402-409); returns the number of edges added
+  int closeLoop(const LoopCandidate& c, const SE2d& trans, double cs) {
+    const bool ok = cs < parameters_.loop_closure_max_cs_divergence;       // :340, :402 (parameters_indoor.yaml:8)
+    loop_log_.push_back({c.q, c.lid, cs, ok});
+    if (!ok) return 0;
+    Constraint e;                                                          // :341-347, :403-409
+    e.id_begin = root_nodes_.at(c.sub_i);
+    e.id_end = c.q;
+    e.trans = trans;
+    const double w = parameters_.loop_closure_weight;
+    e.sqrt_information = {w, 0, 0, 0, w, 0, 0, 0, w};                      // loop_closure_weight * I
+    edges_.push_back(e);
+    return 1;
+  }
+
+  // one candidate the way the reference's loop body handles it, the maps BY VALUE like there
+  int registerAndClose(const LoopCandidate& c, bool global_search) {
+    SE2d trans = c.guess;
+    Map f_loop_map = submaps_.at(c.sub_i);   // :329, :370  (copies: values)
+    Map m_loop_map = scans_.at(c.q);         // :332, :371
+    if (global_search)                       // :379-388
+      ndt_matcher_.estimateTransformGlobalBNB(trans, f_loop_map, m_loop_map, parameters_.use_intensity_in_loop_closure,
+                                              parameters_.loop_closure_scale, c.window_linear, c.window_angular);
+    ndt_matcher_.estimateLoopConstraint(trans, f_loop_map, m_loop_map, parameters_.loop_closure_gnc_steps, parameters_.use_intensity_in_loop_closure,
+                                        parameters_.loop_closure_scale);   // :335, :395
+    m_loop_map.transformMap(trans);                                        // :338, :396
+    const double cs = f_loop_map.calculateCSDivergence(m_loop_map);        // :339, :397
+    return closeLoop(c, trans, cs);
+  }
+
+  // the lists of a batched registration: every candidate submap once, in the order of its first candidate
+  struct StagedCandidates {
+    std::vector<SE2d> trans;
+    std::vector<const Map*> fixed, moving;
+    std::vector<int> fixed_of_pair;
+  };
+  StagedCandidates stageCandidates(const std::vector<LoopCandidate>& cand) const {
+    StagedCandidates s;
+    std::map<int, int> slot_of_submap;
+    for (const LoopCandidate& c : cand) {
+      if (!slot_of_submap.count(c.sub_i)) {
+        slot_of_submap[c.sub_i] = static_cast<int>(s.fixed.size());
+        s.fixed.push_back(&submaps_.at(c.sub_i));
+      }
+      s.fixed_of_pair.push_back(slot_of_submap.at(c.sub_i));
+      s.moving.push_back(&scans_.at(c.q));
+      s.trans.push_back(c.guess);
+    }
+    return s;
+  }
+
+  // behind a batched registration: the gates and the edges in query order, like the sequential loop
+  int gateBatch(const std::vector<LoopCandidate>& cand, const std::vector<SE2d>& trans) {
+    int added = 0;
+    for (size_t p = 0; p < cand.size(); ++p) {
+      Map m_loop_map = scans_.at(cand[p].q);
+      m_loop_map.transformMap(trans[p]);                                                        // :338, :396
+      const double cs = submaps_.at(cand[p].sub_i).calculateCSDivergence(m_loop_map);           // :339, :397
+      added += closeLoop(cand[p], trans[p], cs);
+    }
+    return added;
+  }
+
+  int nextLoopQuery() {
+    const int q = _next_maps_to_search_loop.front();
+    _next_maps_to_search_loop.pop_front();
+    return q;
+  }
+
+ public:
+  // LocalFuser::detectLoopClosures, the branch without Scan Context (local_fuser.cpp:351-412): per candidate optionally
+  // estimateTransformGlobalBNB (:380-387), then the refinement and the CS gate of the other branch
   int detectLoopClosuresCovarianceGated() {
     int added = 0;
-    const double thr = parameters_.max_data_association_mahalanobis_dist;
+    std::vector<LoopCandidate> cand;
     while (!_next_maps_to_search_loop.empty()) {
-      const int q = _next_maps_to_search_loop.front();
-      _next_maps_to_search_loop.pop_front();
-      std::map<int, std::pair<int, double>> best_submap_matches;
-      const Pose& pq = nodes_.at(q);
-      for (const auto& pose_i : nodes_) {
-        const int sub_i = submap_idzs_.at(pose_i.first);
-        if (sub_i == submap_idzs_.at(q) || sub_i == n_finished_submaps_ || !submaps_.count(sub_i)) continue;   // :355
-        const std::array<double, 4>& P = pose_i.second.cov_pos_pos;
-        const double a = P[0], b = P[1], c = P[2], d = P[3], det = a * d - b * c;
-        if (!(a > 0.0 && det > 0.0)) continue;
-        const double dx = pq.pose.d[2] - pose_i.second.pose.d[2], dy = pq.pose.d[3] - pose_i.second.pose.d[3];
-        const double dist = std::sqrt((d * dx * dx - (b + c) * dx * dy + a * dy * dy) / det);                 // :357
-        if (dist < thr) {                                                                                     // :358-362
-          auto it = best_submap_matches.find(sub_i);
-          if (it == best_submap_matches.end() || dist < it->second.second) best_submap_matches[sub_i] = std::make_pair(pose_i.first, dist);
-        }
-      }
-      for (const auto& match : best_submap_matches) {
-        const int sub_i = match.first, lid = match.second.first;
-        Map f_loop_map = submaps_.at(sub_i);   // :370
-        Map m_loop_map = scans_.at(q);         // :371
-        SE2d trans = se2_mul(se2_inv(nodes_.at(root_nodes_.at(sub_i)).pose), pq.pose);   // :376
-        if (parameters_.compute_dfs_loop_closure) {                                       // :379-388
-          const std::array<double, 9>& cov = nodes_.at(lid).cov;
-          const double ca = cov[0], cc = cov[3], cd = cov[4];   // self-adjoint xy block, lower triangle read like Eigen does
-          const double lam0 = 0.5 * (ca + cd) - std::sqrt(0.25 * (ca - cd) * (ca - cd) + cc * cc);   // eigenvalues()(0): the SMALLER one
-          const double search_window_linear = thr * std::abs(lam0);   // named "max" there, and no root is taken: kept
-          const double search_window_angular = std::min(2 * M_PI, thr * std::sqrt(cov[8]));
-          ndt_matcher_.estimateTransformGlobalBNB(trans, f_loop_map, m_loop_map, parameters_.use_intensity_in_loop_closure,
-                                                  parameters_.loop_closure_scale, search_window_linear, search_window_angular);
-        }
-        ndt_matcher_.estimateLoopConstraint(trans, f_loop_map, m_loop_map, parameters_.loop_closure_gnc_steps, parameters_.use_intensity_in_loop_closure,
-                                            parameters_.loop_closure_scale);   // :395
-        m_loop_map.transformMap(trans);                                        // :396
-        const double cs = f_loop_map.calculateCSDivergence(m_loop_map);        // :397
-        const bool ok = cs < parameters_.loop_closure_max_cs_divergence;       // :402
-        loop_log_.push_back({q, lid, cs, ok});
-        if (ok) {                                                              // :403-409
-          Constraint c;
-          c.id_begin = root_nodes_.at(sub_i);
-          c.id_end = q;
-          c.trans = trans;
-          const double w = parameters_.loop_closure_weight;
-          c.sqrt_information = {w, 0, 0, 0, w, 0, 0, 0, w};
-          edges_.push_back(c);
-          ++added;
-        }
-      }
+      cand.clear();
+      covarianceCandidates(nextLoopQuery(), cand);
+      for (const LoopCandidate& c : cand) added += registerAndClose(c, parameters_.compute_dfs_loop_closure);
     }
     return added;
   }
@@ -175,35 +257,9 @@ class LocalFuser {
   int detectLoopClosures() {
     if (covariance_gated_) return detectLoopClosuresCovarianceGated();
     int added = 0;
-    while (!_next_maps_to_search_loop.empty()) {
-      const int q = _next_maps_to_search_loop.front();
-      _next_maps_to_search_loop.pop_front();
-      const std::pair<int, float> det = sc_manager_.detectLoopClosureID(q);   // :323
-      const int lid = det.first;
-      if (lid == -1 || submap_idzs_.at(q) == submap_idzs_.at(lid)) continue;
-      const int sub_i = submap_idzs_.at(lid);
-      if (!submaps_.count(sub_i)) continue;  // submaps_.at() would throw: the candidate's submap is still being built
-      const SE2d root = nodes_.at(root_nodes_.at(sub_i)).pose;
-      SE2d trans = se2_mul(se2_mul(se2_inv(root), nodes_.at(lid).pose), SE2d(-static_cast<double>(det.second), 0.0, 0.0));   // :333
-      Map f_loop_map = submaps_.at(sub_i);   // :329  (copies: values)
-      Map m_loop_map = scans_.at(q);         // :332
-      ndt_matcher_.estimateLoopConstraint(trans, f_loop_map, m_loop_map, parameters_.loop_closure_gnc_steps, parameters_.use_intensity_in_loop_closure,
-                                          parameters_.loop_closure_scale);   // :335
-      m_loop_map.transformMap(trans);                                                     // :338
-      const double cs = f_loop_map.calculateCSDivergence(m_loop_map);                     // :339
-      const bool ok = cs < parameters_.loop_closure_max_cs_divergence;                    // :340 (parameters_indoor.yaml:8)
-      loop_log_.push_back({q, lid, cs, ok});
-      if (ok) {                                                                           // :341-347
-        Constraint c;
-        c.id_begin = root_nodes_.at(sub_i);
-        c.id_end = q;
-        c.trans = trans;
-        const double w = parameters_.loop_closure_weight;
-        c.sqrt_information = {w, 0, 0, 0, w, 0, 0, 0, w};                                 // loop_closure_weight * I
-        edges_.push_back(c);
-        ++added;
-      }
-    }
+    LoopCandidate c;
+    while (!_next_maps_to_search_loop.empty())
+      if (scanContextCandidate(nextLoopQuery(), &c)) added += registerAndClose(c, false);
     return added;
   }
 
@@ -215,56 +271,16 @@ class LocalFuser {
   // graph comes out exactly as from detectLoopClosures() called at the same moments.  Pays when several queries are pending --
   // a search timer slower than the keyframe rate (ndt_slam.cpp:363-365), offline replays.
   int detectLoopClosuresBatched(DeviceGroup& group, int* n_candidates = nullptr) {
-    struct Candidate { int q, lid, sub_i; };
-    std::vector<Candidate> cand;
-    std::vector<SE2d> trans;
-    while (!_next_maps_to_search_loop.empty()) {
-      const int q = _next_maps_to_search_loop.front();
-      _next_maps_to_search_loop.pop_front();
-      const std::pair<int, float> det = sc_manager_.detectLoopClosureID(q);   // :323
-      const int lid = det.first;
-      if (lid == -1 || submap_idzs_.at(q) == submap_idzs_.at(lid)) continue;
-      const int sub_i = submap_idzs_.at(lid);
-      if (!submaps_.count(sub_i)) continue;
-      const SE2d root = nodes_.at(root_nodes_.at(sub_i)).pose;
-      cand.push_back({q, lid, sub_i});
-      trans.push_back(se2_mul(se2_mul(se2_inv(root), nodes_.at(lid).pose), SE2d(-static_cast<double>(det.second), 0.0, 0.0)));   // :333
-    }
+    std::vector<LoopCandidate> cand;
+    LoopCandidate c;
+    while (!_next_maps_to_search_loop.empty())
+      if (scanContextCandidate(nextLoopQuery(), &c)) cand.push_back(c);
     if (n_candidates) *n_candidates = static_cast<int>(cand.size());
     if (cand.empty()) return 0;
-    std::vector<const Map*> fixed, moving;
-    std::vector<int> fixed_of_pair;
-    std::map<int, int> slot_of_submap;
-    for (const Candidate& c : cand) {
-      if (!slot_of_submap.count(c.sub_i)) {
-        slot_of_submap[c.sub_i] = static_cast<int>(fixed.size());
-        fixed.push_back(&submaps_.at(c.sub_i));
-      }
-      fixed_of_pair.push_back(slot_of_submap.at(c.sub_i));
-      moving.push_back(&scans_.at(c.q));
-    }
-    ndt_matcher_.estimateLoopConstraintBatch(group, trans, fixed, fixed_of_pair, moving, parameters_.loop_closure_gnc_steps,
+    StagedCandidates s = stageCandidates(cand);
+    ndt_matcher_.estimateLoopConstraintBatch(group, s.trans, s.fixed, s.fixed_of_pair, s.moving, parameters_.loop_closure_gnc_steps,
                                              parameters_.use_intensity_in_loop_closure, parameters_.loop_closure_scale);   // :335, all at once
-    int added = 0;
-    for (size_t p = 0; p < cand.size(); ++p) {   // the gate and the edges in query order, like the sequential loop
-      const Candidate& c = cand[p];
-      Map m_loop_map = scans_.at(c.q);
-      m_loop_map.transformMap(trans[p]);                                                                  // :338
-      const double cs = submaps_.at(c.sub_i).calculateCSDivergence(m_loop_map);                           // :339
-      const bool ok = cs < parameters_.loop_closure_max_cs_divergence;
-      loop_log_.push_back({c.q, c.lid, cs, ok});
-      if (ok) {
-        Constraint e;
-        e.id_begin = root_nodes_.at(c.sub_i);
-        e.id_end = c.q;
-        e.trans = trans[p];
-        const double w = parameters_.loop_closure_weight;
-        e.sqrt_information = {w, 0, 0, 0, w, 0, 0, 0, w};
-        edges_.push_back(e);
-        ++added;
-      }
-    }
-    return added;
+    return gateBatch(cand, s.trans);
   }
 
   // NOT in the reference: detectLoopClosuresCovarianceGated() with the candidates of ALL pending queries as one batch on the
@@ -273,78 +289,23 @@ class LocalFuser {
   // candidates do not depend on each other and the batched calls are bit-identical to the single ones, so the graph comes out
   // exactly as from detectLoopClosuresCovarianceGated() called at the same moments.
   int detectLoopClosuresCovarianceGatedBatched(int* n_candidates = nullptr) {
-    struct Candidate { int q, lid, sub_i; };
-    std::vector<Candidate> cand;
-    std::vector<SE2d> trans;
-    std::vector<double> windows_linear, windows_angular;
-    const double thr = parameters_.max_data_association_mahalanobis_dist;
-    while (!_next_maps_to_search_loop.empty()) {
-      const int q = _next_maps_to_search_loop.front();
-      _next_maps_to_search_loop.pop_front();
-      std::map<int, std::pair<int, double>> best_submap_matches;
-      const Pose& pq = nodes_.at(q);
-      for (const auto& pose_i : nodes_) {
-        const int sub_i = submap_idzs_.at(pose_i.first);
-        if (sub_i == submap_idzs_.at(q) || sub_i == n_finished_submaps_ || !submaps_.count(sub_i)) continue;   // :355
-        const std::array<double, 4>& P = pose_i.second.cov_pos_pos;
-        const double a = P[0], b = P[1], c = P[2], d = P[3], det = a * d - b * c;
-        if (!(a > 0.0 && det > 0.0)) continue;
-        const double dx = pq.pose.d[2] - pose_i.second.pose.d[2], dy = pq.pose.d[3] - pose_i.second.pose.d[3];
-        const double dist = std::sqrt((d * dx * dx - (b + c) * dx * dy + a * dy * dy) / det);                 // :357
-        if (dist < thr) {                                                                                     // :358-362
-          auto it = best_submap_matches.find(sub_i);
-          if (it == best_submap_matches.end() || dist < it->second.second) best_submap_matches[sub_i] = std::make_pair(pose_i.first, dist);
-        }
-      }
-      for (const auto& match : best_submap_matches) {
-        const int sub_i = match.first, lid = match.second.first;
-        cand.push_back({q, lid, sub_i});
-        trans.push_back(se2_mul(se2_inv(nodes_.at(root_nodes_.at(sub_i)).pose), pq.pose));   // :376
-        const std::array<double, 9>& cov = nodes_.at(lid).cov;                                // :379-388
-        const double ca = cov[0], cc = cov[3], cd = cov[4];
-        const double lam0 = 0.5 * (ca + cd) - std::sqrt(0.25 * (ca - cd) * (ca - cd) + cc * cc);
-        windows_linear.push_back(thr * std::abs(lam0));
-        windows_angular.push_back(std::min(2 * M_PI, thr * std::sqrt(cov[8])));
-      }
-    }
+    std::vector<LoopCandidate> cand;
+    while (!_next_maps_to_search_loop.empty()) covarianceCandidates(nextLoopQuery(), cand);
     if (n_candidates) *n_candidates = static_cast<int>(cand.size());
     if (cand.empty()) return 0;
-    std::vector<const Map*> fixed, moving;
-    std::vector<int> fixed_of_pair;
-    std::map<int, int> slot_of_submap;
-    for (const Candidate& c : cand) {
-      if (!slot_of_submap.count(c.sub_i)) {
-        slot_of_submap[c.sub_i] = static_cast<int>(fixed.size());
-        fixed.push_back(&submaps_.at(c.sub_i));
+    StagedCandidates s = stageCandidates(cand);
+    if (parameters_.compute_dfs_loop_closure) {
+      std::vector<double> windows_linear, windows_angular;
+      for (const LoopCandidate& c : cand) {
+        windows_linear.push_back(c.window_linear);
+        windows_angular.push_back(c.window_angular);
       }
-      fixed_of_pair.push_back(slot_of_submap.at(c.sub_i));
-      moving.push_back(&scans_.at(c.q));
-    }
-    if (parameters_.compute_dfs_loop_closure)
-      ndt_matcher_.estimateTransformGlobalBNBBatch(trans, fixed, fixed_of_pair, moving, parameters_.use_intensity_in_loop_closure,
+      ndt_matcher_.estimateTransformGlobalBNBBatch(s.trans, s.fixed, s.fixed_of_pair, s.moving, parameters_.use_intensity_in_loop_closure,
                                                    parameters_.loop_closure_scale, windows_linear, windows_angular);
-    ndt_matcher_.estimateLoopConstraintBatch(trans, fixed, fixed_of_pair, moving, parameters_.loop_closure_gnc_steps,
-                                             parameters_.use_intensity_in_loop_closure, parameters_.loop_closure_scale);   // :395, all at once
-    int added = 0;
-    for (size_t p = 0; p < cand.size(); ++p) {
-      const Candidate& c = cand[p];
-      Map m_loop_map = scans_.at(c.q);
-      m_loop_map.transformMap(trans[p]);                                                     // :396
-      const double cs = submaps_.at(c.sub_i).calculateCSDivergence(m_loop_map);              // :397
-      const bool ok = cs < parameters_.loop_closure_max_cs_divergence;                       // :402
-      loop_log_.push_back({c.q, c.lid, cs, ok});
-      if (ok) {
-        Constraint e;
-        e.id_begin = root_nodes_.at(c.sub_i);
-        e.id_end = c.q;
-        e.trans = trans[p];
-        const double w = parameters_.loop_closure_weight;
-        e.sqrt_information = {w, 0, 0, 0, w, 0, 0, 0, w};
-        edges_.push_back(e);
-        ++added;
-      }
     }
-    return added;
+    ndt_matcher_.estimateLoopConstraintBatch(s.trans, s.fixed, s.fixed_of_pair, s.moving, parameters_.loop_closure_gnc_steps,
+                                             parameters_.use_intensity_in_loop_closure, parameters_.loop_closure_scale);   // :395, all at once
+    return gateBatch(cand, s.trans);
   }
 
   // NDTSlam::optimizePoseGraph (ndt_slam.cpp:351-361) + the pose part of LocalFuser::updateSubmaps (local_fuser.cpp:65-88)

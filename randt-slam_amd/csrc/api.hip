@@ -1729,6 +1729,58 @@ struct BnbNode {
 };
 void bnb_pose(double a, double tx, double ty, double* out);
 void bnb_mul(const double* a, const double* b, double* out);
+
+// Shared by the single call and the batch, which are held to each other bit for bit: the same libm calls on the same loop
+// variables, accumulated with `+=` like the reference's loops (index * step would give other doubles and so other poses).
+// (static: the file's extern "C" block would export them from an unnamed namespace)
+// The argument checks apart from the windows: a non-positive or non-finite step never ends the grid loops (:527-541, :584-600),
+// csm_linear_step >= 2 csm_max_px_accurate_range makes the angular step NaN (acos argument < -1).
+static bool bnb_params_ok(const randt_matcher_params* mp, const randt_bnb_params* bp, double scale) {
+  return isfinite(bp->csm_linear_step) && bp->csm_linear_step > 0.0 && isfinite(bp->csm_max_px_accurate_range) &&
+         bp->csm_max_px_accurate_range > 0.0 && bp->csm_n_iter >= 1 && bp->csm_n_iter <= 16 && isfinite(bp->csm_window_linear) &&
+         isfinite(bp->csm_window_angular) && isfinite(bp->csm_cost_threshold) && isfinite(scale) && scale > 0.0 &&
+         isfinite(mp->loss_alpha) && bp->csm_linear_step < 2.0 * bp->csm_max_px_accurate_range;
+}
+const char* const kBnbParamsText = "correlative search: steps / ranges must be finite and positive, csm_n_iter in 1..16";
+struct BnbSteps {  // ndt_matcher.cpp:520-526
+  static constexpr int k = 4;  // addNDTFactor(..., 4), :520
+  int n_iter;
+  double linear_step, angular_step, initial_linear_step;
+  explicit BnbSteps(const randt_bnb_params* bp) : n_iter(bp->csm_n_iter), linear_step(bp->csm_linear_step) {
+    const double max_range = bp->csm_max_px_accurate_range;
+    angular_step = acos(1 - ((linear_step * linear_step) / (2 * max_range * max_range)));
+    initial_linear_step = pow(2, (double)n_iter - 1) * linear_step;
+  }
+};
+// the level-1 grid of one pair of windows (after the fmin of :505-506) in the order of the loops :527-541: appends the delta
+// poses of its first `cap` points to `out` and returns how many points it has, -1 from INT32_MAX on
+static int bnb_level1_deltas(const BnbSteps& st, double swl, double swa, int cap, std::vector<double>& out) {
+  int n = 0;
+  double d4[4];
+  for (double tx = -swl / 2.0; tx <= swl / 2.0; tx += st.initial_linear_step)
+    for (double ty = -swl / 2.0; ty <= swl / 2.0; ty += st.initial_linear_step)
+      for (double a = -swa / 2.0; a < swa / 2.0; a += st.angular_step) {
+        if (n < cap) {
+          bnb_pose(a, tx, ty, d4);
+          out.insert(out.end(), d4, d4 + 4);
+        }
+        if (++n == INT32_MAX) return -1;
+      }
+  return n;
+}
+// the 3 x 3 x 3 delta poses from a node of `level` to its children (:584-600), appended to `out`; returns their number
+static int bnb_children_deltas(const BnbSteps& st, int level, std::vector<double>& out) {
+  const double cls = pow(2.0, (double)level) * st.linear_step, cas = st.angular_step;
+  int n = 0;
+  double d4[4];
+  for (double tx = -cls; tx <= cls; tx += cls)
+    for (double ty = -cls; ty <= cls; ty += cls)
+      for (double a = -cas; a <= cas; a += cas, ++n) {
+        bnb_pose(a, tx, ty, d4);
+        out.insert(out.end(), d4, d4 + 4);
+      }
+  return n;
+}
 }  // namespace
 
 int randt_search_global(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, const randt_maps* moving, int moving_idx,
@@ -1736,42 +1788,32 @@ int randt_search_global(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, 
                         double h_trans4[4], double* min_cost_out, int* n_evals) {
   DeviceGuard dev_guard__(ctx);
   if (!ctx || !mp || !bp || !h_trans4 || !range_ok(fixed, fixed_idx, 1) || !range_ok(moving, moving_idx, 1)) return RANDT_ERR_INVALID;
-  // the reference's grid loops advance by these steps (`tx += initial_linear_step`, `a += angular_step`, :527-541,
-  // :584-600): a non-positive or non-finite step never terminates (and the node list grows until memory runs out)
-  if (!(isfinite(bp->csm_linear_step) && bp->csm_linear_step > 0.0) || !(isfinite(bp->csm_max_px_accurate_range) && bp->csm_max_px_accurate_range > 0.0) ||
-      bp->csm_n_iter < 1 || bp->csm_n_iter > 16 || !isfinite(swl) || !isfinite(swa) || !isfinite(bp->csm_window_linear) ||
-      !isfinite(bp->csm_window_angular) || !isfinite(bp->csm_cost_threshold) || !(isfinite(scale) && scale > 0.0) || !isfinite(mp->loss_alpha) ||
-      bp->csm_linear_step >= 2.0 * bp->csm_max_px_accurate_range /* acos argument < -1: angular step NaN */)
-    return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: steps / ranges must be finite and positive, csm_n_iter in 1..16", hipSuccess);
+  if (!bnb_params_ok(mp, bp, scale) || !isfinite(swl) || !isfinite(swa)) return randt_set_error(ctx, RANDT_ERR_INVALID, kBnbParamsText, hipSuccess);
   randt_note_user(ctx, fixed);
   randt_note_user(ctx, moving);
   swl = fmin(swl, bp->csm_window_linear);   // ndt_matcher.cpp:505-506
   swa = fmin(swa, bp->csm_window_angular);
-  const int k = 4;                          // addNDTFactor(..., 4), :520
-  const double linear_step = bp->csm_linear_step, max_range = bp->csm_max_px_accurate_range;
-  const double angular_step = acos(1 - ((linear_step * linear_step) / (2 * max_range * max_range)));
-  const size_t n_iter = (size_t)bp->csm_n_iter;
-  const double initial_linear_step = pow(2, (double)n_iter - 1) * linear_step;
+  const BnbSteps st(bp);
+  const int k = st.k;
   std::vector<BnbNode> level_nodes, next_nodes;
+  std::vector<double> deltas;  // of level 1, then of the children of the level at hand
   std::vector<float> keys;  // std::vector<std::vector<float>> calculated_points, 9 floats each
   auto key_of = [](const double* p, float* key) {
     key[0] = (float)p[0]; key[1] = (float)p[1]; key[2] = 0.f;
     key[3] = (float)(-p[1]); key[4] = (float)p[0]; key[5] = 0.f;
     key[6] = (float)p[2]; key[7] = (float)p[3]; key[8] = 1.f;
   };
-  for (double tx = -swl / 2.0; tx <= swl / 2.0; tx += initial_linear_step)
-    for (double ty = -swl / 2.0; ty <= swl / 2.0; ty += initial_linear_step)
-      for (double a = -swa / 2.0; a < swa / 2.0; a += angular_step) {
-        double d4[4];
-        BnbNode nd;
-        bnb_pose(a, tx, ty, d4);
-        bnb_mul(h_trans4, d4, nd.pose);
-        nd.level = 1;
-        level_nodes.push_back(nd);
-        float key[9];
-        key_of(nd.pose, key);
-        keys.insert(keys.end(), key, key + 9);
-      }
+  const int n_level1 = bnb_level1_deltas(st, swl, swa, INT32_MAX, deltas);
+  if (n_level1 < 0) return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: level-1 grid too large", hipSuccess);
+  for (int i = 0; i < n_level1; ++i) {
+    BnbNode nd;
+    bnb_mul(h_trans4, &deltas[4 * (size_t)i], nd.pose);
+    nd.level = 1;
+    level_nodes.push_back(nd);
+    float key[9];
+    key_of(nd.pose, key);
+    keys.insert(keys.end(), key, key + 9);
+  }
   // association once at the guess (frozen for the whole search, quirk A.7-8)
   double min_cost = 100000.0;
   double best[4] = {1.0, 0.0, 0.0, 0.0};
@@ -1809,37 +1851,32 @@ int randt_search_global(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, 
     RANDT_HIP_CHECK(ctx, randt_sync(ctx));
     evals += P;
     next_nodes.clear();
+    const int cur_level = level_nodes[0].level;  // the queue holds one level at a time: the children of level L are all L + 1
+    deltas.clear();                          // the children's deltas depend on the level alone: once per level, not per node
+    const int n_children = cur_level < st.n_iter ? bnb_children_deltas(st, cur_level, deltas) : 0;
     for (int i = 0; i < P; ++i) {   // FIFO order of the reference's queue (:560-605)
       const double current_cost = h_cost[i] / (double)n_res;
-      const size_t level = (size_t)level_nodes[i].level;
       if (current_cost < bp->csm_cost_threshold) {
         if (current_cost < min_cost) {
           memcpy(best, level_nodes[i].pose, sizeof(best));
           min_cost = current_cost;
         }
-        if (level < n_iter) {
-          const double cls = pow(2.0, (double)level) * linear_step, cas = angular_step;
-          for (double tx = -cls; tx <= cls; tx += cls)
-            for (double ty = -cls; ty <= cls; ty += cls)
-              for (double a = -cas; a <= cas; a += cas) {
-                double d4[4];
-                BnbNode nd;
-                bnb_pose(a, tx, ty, d4);
-                bnb_mul(level_nodes[i].pose, d4, nd.pose);
-                nd.level = (int)level + 1;
-                float key[9];
-                key_of(nd.pose, key);
-                bool found = false;
-                for (size_t t = 0; t + 9 <= keys.size() && !found; t += 9) {  // std::vector<float> ==: element-wise, -0.0f == 0.0f
-                  bool same = true;
-                  for (int c = 0; c < 9 && same; ++c) same = keys[t + c] == key[c];
-                  found = same;
-                }
-                if (!found) {
-                  keys.insert(keys.end(), key, key + 9);
-                  next_nodes.push_back(nd);
-                }
-              }
+        for (int ch = 0; ch < n_children; ++ch) {   // :584-600
+          BnbNode nd;
+          bnb_mul(level_nodes[i].pose, &deltas[4 * (size_t)ch], nd.pose);
+          nd.level = cur_level + 1;
+          float key[9];
+          key_of(nd.pose, key);
+          bool found = false;
+          for (size_t t = 0; t + 9 <= keys.size() && !found; t += 9) {  // std::vector<float> ==: element-wise, -0.0f == 0.0f
+            bool same = true;
+            for (int c = 0; c < 9 && same; ++c) same = keys[t + c] == key[c];
+            found = same;
+          }
+          if (!found) {
+            keys.insert(keys.end(), key, key + 9);
+            next_nodes.push_back(nd);
+          }
         }
       }
     }
@@ -1851,14 +1888,6 @@ int randt_search_global(randt_ctx* ctx, const randt_maps* fixed, int fixed_idx, 
   return RANDT_OK;
 }
 
-// the argument checks of randt_search_global apart from the windows, for the batch entry
-static bool bnb_params_ok(const randt_matcher_params* mp, const randt_bnb_params* bp, double scale) {
-  return isfinite(bp->csm_linear_step) && bp->csm_linear_step > 0.0 && isfinite(bp->csm_max_px_accurate_range) &&
-         bp->csm_max_px_accurate_range > 0.0 && bp->csm_n_iter >= 1 && bp->csm_n_iter <= 16 && isfinite(bp->csm_window_linear) &&
-         isfinite(bp->csm_window_angular) && isfinite(bp->csm_cost_threshold) && isfinite(scale) && scale > 0.0 &&
-         isfinite(mp->loss_alpha) && bp->csm_linear_step < 2.0 * bp->csm_max_px_accurate_range;
-}
-
 int randt_search_global_batch_dev(randt_ctx* ctx, const randt_maps* fixed, const int32_t* d_fixed_idx, const randt_maps* moving,
                                   int moving_first, int n_pairs, const randt_matcher_params* mp, const randt_bnb_params* bp,
                                   double scale, const double* h_wl, const double* h_wa, int max_nodes, double* d_trans4,
@@ -1867,19 +1896,15 @@ int randt_search_global_batch_dev(randt_ctx* ctx, const randt_maps* fixed, const
   if (!ctx || !fixed || !mp || !bp || !d_fixed_idx || !h_wl || !h_wa || !d_trans4 || !d_results || n_pairs < 1 || max_nodes < 1 ||
       !range_ok(moving, moving_first, n_pairs))
     return RANDT_ERR_INVALID;
-  if (!bnb_params_ok(mp, bp, scale))
-    return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: steps / ranges must be finite and positive, csm_n_iter in 1..16", hipSuccess);
+  if (!bnb_params_ok(mp, bp, scale)) return randt_set_error(ctx, RANDT_ERR_INVALID, kBnbParamsText, hipSuccess);
   for (int p = 0; p < n_pairs; ++p)
     if (!isfinite(h_wl[p]) || !isfinite(h_wa[p]))
       return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: the search windows must be finite", hipSuccess);
   if (n_pairs > 65535) return randt_set_error(ctx, RANDT_ERR_UNSUPPORTED, "correlative search: at most 65535 pairs per call", hipSuccess);
   randt_note_user(ctx, fixed);
   randt_note_user(ctx, moving);
-  const int k = 4;  // addNDTFactor(..., 4), :520
-  const int n_iter = bp->csm_n_iter;
-  const double linear_step = bp->csm_linear_step, max_range = bp->csm_max_px_accurate_range;
-  const double angular_step = acos(1 - ((linear_step * linear_step) / (2 * max_range * max_range)));
-  const double initial_linear_step = pow(2, (double)n_iter - 1) * linear_step;
+  const BnbSteps st(bp);
+  const int k = st.k, n_iter = st.n_iter;
   // one level-1 delta table per distinct pair of windows (after the fmin of :505-506), in the order of the loops :527-541.  A
   // grid larger than max_nodes is only counted: its pairs are flagged by the seed kernel.
   struct Grid { double swl, swa; int first, n; };
@@ -1893,16 +1918,8 @@ int randt_search_global_batch_dev(randt_ctx* ctx, const randt_maps* fixed, const
     while (g < grids.size() && !(grids[g].swl == swl && grids[g].swa == swa)) ++g;
     if (g == grids.size()) {
       Grid ng{swl, swa, (int)(tables.size() / 4), 0};
-      for (double tx = -swl / 2.0; tx <= swl / 2.0; tx += initial_linear_step)
-        for (double ty = -swl / 2.0; ty <= swl / 2.0; ty += initial_linear_step)
-          for (double a = -swa / 2.0; a < swa / 2.0; a += angular_step) {
-            if (ng.n < max_nodes) {
-              double d4[4];
-              bnb_pose(a, tx, ty, d4);
-              tables.insert(tables.end(), d4, d4 + 4);
-            }
-            if (++ng.n == INT32_MAX) return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: level-1 grid too large", hipSuccess);
-          }
+      ng.n = bnb_level1_deltas(st, swl, swa, max_nodes, tables);
+      if (ng.n < 0) return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: level-1 grid too large", hipSuccess);
       if (ng.n > max_nodes) tables.resize(4 * (size_t)ng.first);
       grids.push_back(ng);
     }
@@ -1911,18 +1928,9 @@ int randt_search_global_batch_dev(randt_ctx* ctx, const randt_maps* fixed, const
     if (grids[g].n <= max_nodes && grids[g].n > level1_bound) level1_bound = grids[g].n;
   }
   const size_t level1_doubles = tables.size();
-  for (int level = 1; level < n_iter; ++level) {
-    const double cls = pow(2.0, (double)level) * linear_step, cas = angular_step;
-    int n = 0;
-    for (double tx = -cls; tx <= cls; tx += cls)
-      for (double ty = -cls; ty <= cls; ty += cls)
-        for (double a = -cas; a <= cas; a += cas, ++n) {
-          double d4[4];
-          bnb_pose(a, tx, ty, d4);
-          tables.insert(tables.end(), d4, d4 + 4);
-        }
-    if (n != 27) return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: a level's step grid is not 3 x 3 x 3", hipSuccess);
-  }
+  for (int level = 1; level < n_iter; ++level)
+    if (bnb_children_deltas(st, level, tables) != 27)
+      return randt_set_error(ctx, RANDT_ERR_INVALID, "correlative search: a level's step grid is not 3 x 3 x 3", hipSuccess);
   // The workspace is grow-only context memory of 60 B x n_pairs x max_nodes (keys 16, poses 32, costs 8, admitted 4) plus the
   // correspondence tables: 7.5 MB for 64 pairs at max_nodes 2048, 250 MB for 512 pairs at the default 8192 -- callers with large
   // batches and shallow searches pass a max_nodes that fits them (an overflowing pair is flagged, not wrong).

@@ -111,27 +111,29 @@ class Slam(Odometry):
         return True
 
     # ---- LocalFuser::detectLoopClosures, Scan Context branch (:318-350) ------------------------
+    def _scan_context_candidate(self, q):
+        """The candidate of query node q as (q, candidate node, submap, guess), or None."""
+        lid, yaw = self.b.sc_detect(q)                                                                # :323
+        if lid == -1 or self.submap_idzs[q] == self.submap_idzs[lid]:
+            return None
+        sub_i = self.submap_idzs[lid]
+        if sub_i not in self.submaps:          # submaps_.at() would throw: the candidate's submap is still being built
+            return None
+        root = self.nodes[self.root_nodes[sub_i]]
+        return q, lid, sub_i, _se2_mul4(_se2_mul4(_se2_inv4(root), self.nodes[lid]), _pose4(-yaw, 0.0, 0.0))   # :333
+
     def detect_loop_closures(self):
         if self.loop_search == "covariance":
             return self._detect_loop_closures_covariance()
         added = 0
         while self.pending_loop_search:
-            q = self.pending_loop_search.pop(0)
-            lid, yaw = self.b.sc_detect(q)
-            if lid == -1 or self.submap_idzs[q] == self.submap_idzs[lid]:
+            cand = self._scan_context_candidate(self.pending_loop_search.pop(0))
+            if cand is None:
                 continue
-            sub_i = self.submap_idzs[lid]
-            if sub_i not in self.submaps:          # submaps_.at() would throw: the candidate's submap is still being built
-                continue
-            root = self.nodes[self.root_nodes[sub_i]]
-            guess = _se2_mul4(_se2_mul4(_se2_inv4(root), self.nodes[lid]), _pose4(-yaw, 0.0, 0.0))      # :333
+            q, lid, sub_i, guess = cand
             est, _cost = self.b.register_pair(self.submaps[sub_i], self.node_scans[q], self.loop_mp, guess)   # :335
             cs = self.b.cs_divergence(self.submaps[sub_i], self.node_scans[q], est)                     # :338-339
-            ok = bool(cs < self.max_cs)
-            self.loop_log.append((q, lid, float(cs), ok))
-            if ok:
-                self.edges.append((self.root_nodes[sub_i], q, np.array(est, dtype=np.float64), self.loop_sqrt_info))   # :341-347
-                added += 1
+            added += self._close_loop(q, lid, sub_i, est, cs)                                           # :340-347
         return added
 
     # ---- LocalFuser::detectLoopClosures, the branch without Scan Context (:351-412), quirks included -------
@@ -167,7 +169,7 @@ class Slam(Odometry):
         ok = bool(cs < self.max_cs)
         self.loop_log.append((q, lid, float(cs), ok))
         if ok:
-            self.edges.append((self.root_nodes[sub_i], q, np.array(est, dtype=np.float64), self.loop_sqrt_info))   # :402-409
+            self.edges.append((self.root_nodes[sub_i], q, np.array(est, dtype=np.float64), self.loop_sqrt_info))   # :341-347, :402-409
         return int(ok)
 
     def _detect_loop_closures_covariance(self):

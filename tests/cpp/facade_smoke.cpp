@@ -3,6 +3,7 @@
 // Matcher::estimateLoopConstraint.  Exit 0: pose recovered; 3: no GPU (expected on a CPU-only box).
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <deque>
 #include <random>
 #include <vector>
@@ -396,6 +397,45 @@ int main() {
                    batch[p].d[2] == single[p].d[2] && batch[p].d[3] == single[p].d[3];
       std::printf("group of %d: %d candidates, pose[6] %.5f %.5f (single %.5f %.5f), transport %d\n", grp.size(), n_cand, batch[6].d[2],
                   batch[6].d[3], single[6].d[2], single[6].d[3], grp.transport());
+    }
+    // the group form checks fixed_of_pair like the one-context form: an index outside fixed_ndts is refused before anything is
+    // staged or launched, every trans untouched; the same two small pairs with valid indices are the single calls' bit for bit
+    {
+      const int blob = 20 * 4, n_small = 5 * blob;   // five blobs = a few cells per map
+      Map small_scan[2], small_fixed[2], small_moving[2];
+      for (int i = 0; i < 2; ++i) {
+        small_scan[i].initialize(ctx, mp, 0.0, 0.0, 64);
+        small_scan[i].addScan(fixed_pts.data() + i * n_small, n_small / 4, 4, 3, rp);
+        small_fixed[i].initialize(ctx, mp, 0.0, 0.0);
+        small_fixed[i].mergeMapCell(small_scan[i]);
+        small_moving[i].initialize(ctx, mp, 0.0, 0.0, 64);
+        small_moving[i].addScan(moving_pts.data() + i * n_small, n_small / 4, 4, 3, rp);
+      }
+      const std::vector<SE2d> g2{SE2d(0.05, 0.15, -0.05), SE2d(0.08, 0.25, -0.15)};
+      std::vector<SE2d> one = g2;
+      double one_cost[2];
+      for (int p = 0; p < 2; ++p) one_cost[p] = matcher.estimateLoopConstraint(one[p], small_fixed[p], small_moving[p], 2, true, 1.5);
+      DeviceGroup grp(std::vector<int>(2, 0));
+      const std::vector<const Map*> fixed_list{&small_fixed[0], &small_fixed[1]}, moving_list{&small_moving[0], &small_moving[1]};
+      auto same_pose = [](const SE2d& a, const SE2d& b) { return std::memcmp(a.d, b.d, sizeof(a.d)) == 0; };
+      bool refused[2];
+      const std::vector<int> bad_index[2] = {{0, 2}, {-1, 0}};
+      for (int t = 0; t < 2; ++t) {
+        std::vector<SE2d> tr = g2;
+        clear_errors();
+        const std::vector<double> c = matcher.estimateLoopConstraintBatch(grp, tr, fixed_list, bad_index[t], moving_list, 2, true, 1.5);
+        refused[t] = last_status() == RANDT_ERR_INVALID && c.size() == 2 && std::isnan(c[0]) && std::isnan(c[1]) && same_pose(tr[0], g2[0]) &&
+                     same_pose(tr[1], g2[1]);
+      }
+      clear_errors();
+      std::vector<SE2d> tr = g2;
+      const std::vector<double> c = matcher.estimateLoopConstraintBatch(grp, tr, fixed_list, {0, 1}, moving_list, 2, true, 1.5);
+      bool identical = last_status() == RANDT_OK && c.size() == 2;
+      for (int p = 0; p < 2 && identical; ++p) identical = std::memcmp(&c[p], &one_cost[p], sizeof(double)) == 0 && same_pose(tr[p], one[p]);
+      std::printf("group batch, fixed_of_pair out of range refused: %d %d, in range identical to the single calls: %d (%u + %u, %u + %u cells)\n",
+                  (int)refused[0], (int)refused[1], (int)identical, small_fixed[0].get_n_cells(), small_moving[0].get_n_cells(),
+                  small_fixed[1].get_n_cells(), small_moving[1].get_n_cells());
+      batch_ok = batch_ok && refused[0] && refused[1] && identical;
     }
     // use_analytic_expressions_for_optimization: true -> the reference's hand-written functors on (pos, rot) blocks
     // (RANDT_PARAM_ANALYTIC: their inexact rotation Jacobian reproduced as written): converges next to the autodiff answer

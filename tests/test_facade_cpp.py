@@ -40,3 +40,6 @@ def test_facade_registers_on_gpu(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     assert "WARNING: NO RESIDUALS ADDED!" in r.stdout
     assert "gnc_divisor" in r.stdout and "previous value kept" in r.stdout      # never-throw mode: warnings, not exceptions
+    # the group form of estimateLoopConstraintBatch: fixed_of_pair {0, 2} and {-1, 0} refused with every trans untouched, {0, 1} the single calls
+    assert "fixed_of_pair out of range refused: 1 1, in range identical to the single calls: 1" in r.stdout
+    assert r.stdout.count("WARNING: estimateLoopConstraintBatch: group / argument sizes: invalid argument") == 2
