@@ -29,6 +29,9 @@
 //   * model-cost change (wavefront 1), Plus on every manifold block (wavefront 0), convergence tests / accept-reject /
 //     radius update redundantly by every lane from broadcast scalars (uniform control flow).
 // The candidate point is evaluated with its Jacobians so that an accepted step costs one pass.
+// The GNC x trust-region control flow is in k_solve_window below; window_gen.hip carries a second copy of it for its own data
+// structures (a correction to one has to be made in both).  Shared with that kernel, in window_math.h: the factors, Plus, the
+// decision trace (trace_push) and the dispatch over the eight (D, AM2, ANALYTIC) instantiations (dispatch_window_kernel).
 #include <float.h>
 
 #include "randt_internal.h"
@@ -57,11 +60,7 @@ extern "C" int randt_debug_win_timing(long long* out) {
 #define WIN_FACTOR_WAVE 6
 #define WIN_SPARE_WAVE 2
 __device__ __forceinline__ int ndt_share_of_wave(int wave) {  // 0..5 = share (term = share / wpt, part = share % wpt), -1: none
-#ifdef RANDT_WIN_PLAIN_ROLES
-  return wave == 7 ? 5 : (wave == 2 ? -1 : (wave < 2 ? wave : (wave < 6 ? wave - 1 : -1)));  // 0 1 . 2 3 4 F 5
-#else
   return wave == 0 ? 0 : (wave == 4 ? 1 : (wave == 1 ? 2 : (wave == 5 ? 3 : (wave == 3 ? 4 : (wave == 7 ? 5 : -1)))));
-#endif
 }
 #define WIN_NMAX 32  // tangent dimensions
 #define WIN_SMAX 3   // optimised states
@@ -524,18 +523,6 @@ __device__ void assemble(const WinDesc& W, Shared& sh, int buf, const double* rs
   __syncthreads();
 }
 
-__device__ __forceinline__ void trace_push(double* tr, int max_len, double cost, double radius, int flag) {
-  if (tr && threadIdx.x == 0) {
-    const int n = (int)tr[0];
-    if (3 * (n + 1) + 1 <= max_len) {
-      tr[1 + 3 * n + 0] = cost;
-      tr[1 + 3 * n + 1] = radius;
-      tr[1 + 3 * n + 2] = (double)flag;
-      tr[0] = (double)(n + 1);
-    }
-  }
-}
-
 // The damped solve (H_s + D / radius) y = g_s by the banded block Gauss-Jordan (band_pivot above), one wavefront per LEVEL:
 // level 0 is the radius of the running iteration, level q the radius q rejections later (radius / decrease, decrease doubling).
 // A rejected -- or invalid -- step changes nothing but the radius, and with Ceres' default initial radius of 1e4 more than half
@@ -747,9 +734,6 @@ __global__ __launch_bounds__(WIN_BLOCK) void k_solve_window(MapView fixed, MapVi
         okb &= (bstart(j + 1) - bstart(j) <= 8) ? 1 : 0;
         sh.bsize[j] = bstart(j + 1) - bstart(j);
       }
-#ifdef RANDT_WIN_NO_BAND
-      okb = 0;
-#endif
       sh.band_ok = okb;
       sh.cst[0] = 0.0;
       sh.cst[1] = 1.0;
@@ -757,9 +741,6 @@ __global__ __launch_bounds__(WIN_BLOCK) void k_solve_window(MapView fixed, MapVi
       for (int i = 0; i < 8; ++i)
         for (int k = 0; k < 8; ++k)
           if (i != k && W.sqrtI[i * 8 + k] != 0.0) dgl = 0;
-#ifdef RANDT_WIN_NO_DIAG
-      dgl = 0;
-#endif
       sh.sq_diag = dgl;
       for (int i = 0; i < 8; ++i) sh.d2[i] = W.sqrtI[i * 8 + i] * W.sqrtI[i * 8 + i];
     }
@@ -1005,9 +986,6 @@ __global__ __launch_bounds__(WIN_BLOCK) void k_solve_window(MapView fixed, MapVi
           // (Ceres' initial radius 1e4 is shrunk five times before the first step of every GNC step is accepted) and after a
           // rejection; behind an accepted step the next one is usually accepted too and the wavefront solves alone.
           n_lvl = (band_ok && (iteration <= 1 || !step_ok)) ? WIN_LEVELS : 1;
-#ifdef RANDT_WIN_NO_SPEC
-          n_lvl = 1;
-#endif
           if (wave < n_lvl) {
             double rr = radius, dc = decrease;  // the reference's update, replayed: radius /= decrease; decrease *= 2
             for (int q = 0; q < wave; ++q) {
@@ -1018,6 +996,7 @@ __global__ __launch_bounds__(WIN_BLOCK) void k_solve_window(MapView fixed, MapVi
             WT(8);
 #ifndef RANDT_WIN_REPEAT_SOLVE
 #define RANDT_WIN_REPEAT_SOLVE 1  // > 1: cost probe (the solve is idempotent: same inputs, same outputs)
+// (the loop of one trip is not free to drop: without it every instantiation compiles to different code -- HISTORY section 15)
 #endif
 #pragma nounroll
             for (int rpt = 0; rpt < RANDT_WIN_REPEAT_SOLVE; ++rpt)
@@ -1139,22 +1118,11 @@ int launch_solve_window(randt_ctx* ctx, const MapView& fixed, const MapView& mov
   // more than three optimised states (no shipped configuration): the general kernel
   if (desc.n_tan > WIN_NMAX || desc.S > WIN_SMAX || desc.n_terms > 6 || ctx->window_general)
     return launch_solve_window_gen(ctx, fixed, moving, desc, d_desc, d_corr, P, d_states, d_result, n_windows, corr_stride, state_stride);
-#define RANDT_WIN_LAUNCH(DD, AA, NN)                                                                                       \
-  hipLaunchKernelGGL((k_solve_window<DD, AA, NN>), dim3(n_windows), dim3(WIN_BLOCK), 0, ctx->stream, fixed, moving, d_desc, d_corr, P, \
-                     d_states, d_result, ctx->d_trace, ctx->trace_len, corr_stride, state_stride)
-  const bool am2 = P.alpha == -2.0;
-  if (desc.pad_) {  // RANDT_PARAM_ANALYTIC: the reference's hand-written NDT functor (never set by a shipped configuration)
-    if (desc.d3) {
-      if (am2) RANDT_WIN_LAUNCH(3, true, true); else RANDT_WIN_LAUNCH(3, false, true);
-    } else {
-      if (am2) RANDT_WIN_LAUNCH(2, true, true); else RANDT_WIN_LAUNCH(2, false, true);
-    }
-  } else if (desc.d3) {
-    if (am2) RANDT_WIN_LAUNCH(3, true, false); else RANDT_WIN_LAUNCH(3, false, false);
-  } else {
-    if (am2) RANDT_WIN_LAUNCH(2, true, false); else RANDT_WIN_LAUNCH(2, false, false);
-  }
-#undef RANDT_WIN_LAUNCH
+  dispatch_window_kernel(desc, P, [&](auto d, auto am2, auto analytic) {
+    hipLaunchKernelGGL((k_solve_window<decltype(d)::value, decltype(am2)::value, decltype(analytic)::value>), dim3(n_windows),
+                       dim3(WIN_BLOCK), 0, ctx->stream, fixed, moving, d_desc, d_corr, P, d_states, d_result, ctx->d_trace, ctx->trace_len,
+                       corr_stride, state_stride);
+  });
   RANDT_HIP_CHECK(ctx, hipGetLastError());
   return RANDT_OK;
 }

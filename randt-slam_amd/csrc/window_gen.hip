@@ -5,8 +5,9 @@
 // takes any lag (src/ndt_registration/ndt_matcher.cpp:343 smoothing_steps_iter = min(trajectory.size() - 1, smoothing_steps);
 // the parameter is read without a bound, src/ndt_slam/ndt_slam.cpp:576), so this kernel covers the rest: 4..7 optimised
 // states, <= 2 fixed maps (<= 14 NDT terms), <= 68 tangent dimensions.  Same problem wiring, factors (window_math.h), loss,
-// GNC loop and Ceres 2.1.0 trust-region decisions as window.hip -- the control flow below is that kernel's, statement for
-// statement -- with data structures sized by the lag instead of hand-placed:
+// GNC loop and Ceres 2.1.0 trust-region decisions as window.hip -- k_solve_window_gen below holds its own copy of that
+// kernel's control flow (a correction to one has to be made in both; trace_push and the dispatch over the instantiations
+// are window_math.h's) -- with data structures sized by the lag instead of hand-placed:
 //   * one 512-thread workgroup per window.  Wavefronts 0..6 stream the NDT terms (term q on wavefront q mod 7: cell
 //     records straight from device memory, ten fp64 base sums per term); wavefront 7 evaluates the motion / IMU factors, one
 //     lane per factor, at the same time;
@@ -384,18 +385,6 @@ __device__ void gen_band_solve(GShared& sh, int n, int lane, double inv_radius, 
   if (lane == 0) sh.solved[q] = (okf != 0.0 && fin != 0.0) ? 1.0 : 0.0;
 }
 
-__device__ __forceinline__ void trace_push(double* tr, int max_len, double cost, double radius, int flag) {
-  if (tr && threadIdx.x == 0) {
-    const int n = (int)tr[0];
-    if (3 * (n + 1) + 1 <= max_len) {
-      tr[1 + 3 * n + 0] = cost;
-      tr[1 + 3 * n + 1] = radius;
-      tr[1 + 3 * n + 2] = (double)flag;
-      tr[0] = (double)(n + 1);
-    }
-  }
-}
-
 template <int D, bool AM2, bool ANALYTIC>
 __global__ __launch_bounds__(GEN_BLOCK) void k_solve_window_gen(MapView fixed, MapView moving, const WinDesc* __restrict__ Wp,
                                                                 const int32_t* __restrict__ corr, SolveParams P,
@@ -702,22 +691,11 @@ int GEN_LAUNCHER(randt_ctx* ctx, const MapView& fixed, const MapView& moving, co
   if (desc.S > GEN_SMAX) return launch_solve_window_gen_big(ctx, fixed, moving, desc, d_desc, d_corr, P, d_states, d_result, n_windows, corr_stride, state_stride);
 #endif
   if (desc.n_tan > GEN_NMAX || desc.S > GEN_SMAX || desc.n_terms > GEN_TMAX) return randt_set_error(ctx, RANDT_ERR_UNSUPPORTED, GEN_LIMIT_TEXT, hipSuccess);
-#define RANDT_GEN_LAUNCH(DD, AA, NN)                                                                                             \
-  hipLaunchKernelGGL((k_solve_window_gen<DD, AA, NN>), dim3(n_windows), dim3(GEN_BLOCK), 0, ctx->stream, fixed, moving, d_desc, d_corr, P, \
-                     d_states, d_result, ctx->d_trace, ctx->trace_len, corr_stride, state_stride)
-  const bool am2 = P.alpha == -2.0;
-  if (desc.pad_) {  // RANDT_PARAM_ANALYTIC
-    if (desc.d3) {
-      if (am2) RANDT_GEN_LAUNCH(3, true, true); else RANDT_GEN_LAUNCH(3, false, true);
-    } else {
-      if (am2) RANDT_GEN_LAUNCH(2, true, true); else RANDT_GEN_LAUNCH(2, false, true);
-    }
-  } else if (desc.d3) {
-    if (am2) RANDT_GEN_LAUNCH(3, true, false); else RANDT_GEN_LAUNCH(3, false, false);
-  } else {
-    if (am2) RANDT_GEN_LAUNCH(2, true, false); else RANDT_GEN_LAUNCH(2, false, false);
-  }
-#undef RANDT_GEN_LAUNCH
+  dispatch_window_kernel(desc, P, [&](auto d, auto am2, auto analytic) {
+    hipLaunchKernelGGL((k_solve_window_gen<decltype(d)::value, decltype(am2)::value, decltype(analytic)::value>), dim3(n_windows),
+                       dim3(GEN_BLOCK), 0, ctx->stream, fixed, moving, d_desc, d_corr, P, d_states, d_result, ctx->d_trace, ctx->trace_len,
+                       corr_stride, state_stride);
+  });
   RANDT_HIP_CHECK(ctx, hipGetLastError());
   return RANDT_OK;
 }

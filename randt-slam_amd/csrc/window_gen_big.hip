@@ -2,6 +2,7 @@
 // smoothing_steps without a bound (src/ndt_slam/ndt_slam.cpp:576, src/ndt_registration/ndt_matcher.cpp:343).  Same source, larger
 // band (9 S + 5 <= 113 tangent dimensions, <= 24 NDT terms) and ONE Cholesky workspace instead of six -- 142 KB of the CU's
 // 160 KB of LDS: a rejection chain's radii are solved one after the other.  Not tuned; it exists so that such a lag is not refused.
+// (Control flow: k_solve_window_gen in window_gen.hip.)
 #define GEN_SMAX 12
 #define GEN_NMAX 120
 #define GEN_TMAX 24

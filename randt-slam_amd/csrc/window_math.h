@@ -1,8 +1,11 @@
 // Device math shared by the two fixed-lag window kernels (window.hip: the tuned <= 3-state kernel; window_gen.hip: the
 // general one for smoothing_steps > 3): Sophus SE(2) pieces, the motion / IMU factors of both parameterisations with their
-// analytic Jacobians, the state record layout.  Reference formulas: include/ndt_registration/ceres_residuals.h:25-83,
+// analytic Jacobians, the state record layout, the decision trace and the launch dispatch over the kernels' eight
+// instantiations.  Reference formulas: include/ndt_registration/ceres_residuals.h:25-83,
 // 307-370, 554-679; Sophus 1.22.10 se2.hpp / so2.hpp (un-vendored).
 #pragma once
+#include <type_traits>
+
 #include "randt_internal.h"
 #include "solve_math.h"
 
@@ -382,6 +385,39 @@ __device__ double ambient_sq(const WinDesc& W, const SH& sh, int a, int b, int l
       }
   }
   return wave_sum(v);
+}
+
+
+// ---------------------------------------------------------------- shared by the window kernels (window.hip, window_gen.hip) -------
+// decision trace: tr[0] = entries so far, entry i = (cost, radius, flag) at tr[1 + 3 i]
+__device__ __forceinline__ void trace_push(double* tr, int max_len, double cost, double radius, int flag) {
+  if (tr && threadIdx.x == 0) {
+    const int n = (int)tr[0];
+    if (3 * (n + 1) + 1 <= max_len) {
+      tr[1 + 3 * n + 0] = cost;
+      tr[1 + 3 * n + 1] = radius;
+      tr[1 + 3 * n + 2] = (double)flag;
+      tr[0] = (double)(n + 1);
+    }
+  }
+}
+
+// launch(integral_constant<int, D>, bool_constant<AM2>, bool_constant<ANALYTIC>) for the window's instantiation of a kernel
+// template <int D, bool AM2, bool ANALYTIC>.  AM2: Barron shape exactly -2 (the shipped configurations): closed-form loss;
+// ANALYTIC: RANDT_PARAM_ANALYTIC, the reference's hand-written NDT functor (never set by a shipped configuration).
+template <int D, class F>
+inline void dispatch_window_loss(bool am2, bool analytic, F& launch) {
+  using DD = std::integral_constant<int, D>;
+  if (analytic) {
+    if (am2) launch(DD{}, std::true_type{}, std::true_type{}); else launch(DD{}, std::false_type{}, std::true_type{});
+  } else {
+    if (am2) launch(DD{}, std::true_type{}, std::false_type{}); else launch(DD{}, std::false_type{}, std::false_type{});
+  }
+}
+template <class F>
+inline void dispatch_window_kernel(const WinDesc& desc, const SolveParams& P, F&& launch) {
+  const bool am2 = P.alpha == -2.0;
+  if (desc.d3) dispatch_window_loss<3>(am2, desc.pad_ != 0, launch); else dispatch_window_loss<2>(am2, desc.pad_ != 0, launch);
 }
 
 }  // namespace randt_window

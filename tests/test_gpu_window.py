@@ -108,7 +108,9 @@ def test_predict_state_matches_oracle(built):
             assert np.allclose(a[f], b[f], rtol=0, atol=1e-15), f
 
 
-def _run_drive(drive, n_fixed=1, use_imu=0, const_vel=1, trace=True, mp_over=None, param=R.PARAM_MANIFOLD, lag=3):
+def _run_drive(drive, n_fixed=1, use_imu=0, const_vel=1, trace=True, mp_over=None, param=R.PARAM_MANIFOLD, lag=3, check_truth=True):
+    """Returns (states of the drive, every window's randt_result).  check_truth=False drops the truth-tracking assertion at the
+    end (parameter sets under which the oracle itself leaves the truth)."""
     torch, ctx = drive["torch"], drive["ctx"]
     vec = param in (R.PARAM_VECTOR, R.PARAM_ANALYTIC)
     mp = R.default_matcher_params(parameterization=param, gnc_steps=3, **(mp_over or {}))
@@ -119,7 +121,7 @@ def _run_drive(drive, n_fixed=1, use_imu=0, const_vel=1, trace=True, mp_over=Non
     gs, os_ = [s0], [s0.astype(po.STATE_DTYPE)]
     gtrans = otrans = synth.pose3_to_pose4(truth[0])
     fixed_o = [drive["osub"], drive["osub2"]][:n_fixed]
-    imu_all = []
+    imu_all, results = [], []
     dev_trace = torch.zeros(3 * 512 + 1, dtype=torch.float64, device="cuda:0")
     for i in range(1, len(truth)):
         gs.append(R.predict_state(gs[-1], i * dt, R.PARAM_VECTOR if vec else R.PARAM_MANIFOLD))
@@ -162,13 +164,15 @@ def _run_drive(drive, n_fixed=1, use_imu=0, const_vel=1, trace=True, mp_over=Non
         for j in range(S + 1):
             gs[len(gs) - S - 1 + j] = g_states[j]
             os_[len(os_) - S - 1 + j] = o_states[j]
+        results.append(g_res)
         est = synth.pose4_to_pose3(gtrans)
-        assert np.all(np.abs(est[:2] - truth[i][:2]) < 0.08) and abs(synth.wrap_angle(est[2] - truth[i][2])) < 0.03
-    return gs
+        if check_truth:
+            assert np.all(np.abs(est[:2] - truth[i][:2]) < 0.08) and abs(synth.wrap_angle(est[2] - truth[i][2])) < 0.03
+    return gs, results
 
 
 def test_window_drive_matches_oracle(drive):
-    gs = _run_drive(drive)
+    gs, _ = _run_drive(drive)
     assert abs(np.hypot(*gs[-1]["lin_vel"]) - 1.0) < 0.15       # the smoother recovered the 1 m/s body speed
 
 
@@ -223,6 +227,23 @@ def test_general_window_kernel_on_three_state_windows(drive_general, kw):
     _run_drive(drive_general, **kw)
 
 
+# ---- the exits of the trust-region loop other than function tolerance, on both kernels (window.hip, window_gen.hip)
+@pytest.mark.parametrize("lag", [3, 5])
+@pytest.mark.parametrize("mp_over,code,check_truth", [
+    (dict(max_iterations=3), 5, True),             # NO_CONVERGENCE; oracle: 12 iterations per window
+    (dict(min_radius=2e3), 4, True),               # CONVERGENCE_RADIUS; 9..11
+    (dict(parameter_tolerance=1e-2), 2, True),     # CONVERGENCE_PARAMETER; 14..20
+    (dict(gradient_tolerance=1e3), 3, False),      # CONVERGENCE_GRADIENT; 3, no step taken: the oracle itself drifts 0.31 m
+])
+def test_window_stopping_tests_match_oracle(drive, lag, mp_over, code, check_truth):
+    """Every window of the drive ends on the stated Ceres termination type, at lag 3 (window.hip) and lag 5 (window_gen.hip, from
+    the fourth window on), with states, iteration counts and decision traces equal to the oracle's (_run_drive).  Without these
+    cases every window test ends on function tolerance.  HandleInvalidStep (trace flag 3) and FAILURE are not covered: no
+    parameter set made the oracle take them on this drive, an LM diagonal clamped to 1e-300 included."""
+    _, results = _run_drive(drive, lag=lag, mp_over=mp_over, check_truth=check_truth)
+    assert len(results) == 7 and [int(r["termination"]) for r in results] == [code] * 7
+
+
 def test_window_lag_beyond_the_device_solver_is_refused(drive):
     ctx = drive["ctx"]
     mp = R.default_matcher_params(parameterization=R.PARAM_MANIFOLD, gnc_steps=3)
@@ -260,7 +281,7 @@ def test_vector_predict_state_matches_oracle(built):
 
 
 def test_vector_window_drive_matches_oracle(drive):
-    gs = _run_drive(drive, param=R.PARAM_VECTOR)
+    gs, _ = _run_drive(drive, param=R.PARAM_VECTOR)
     assert abs(np.hypot(*gs[-1]["lin_vel"]) - 1.0) < 0.15
 
 
