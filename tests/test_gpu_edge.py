@@ -283,7 +283,8 @@ def test_association_beyond_the_shipped_window_and_neighbour_counts(env, res, si
 
 def test_whole_registration_with_a_wide_window_and_twelve_neighbours(env):
     """estimateLoopConstraint end to end on such a configuration: 0.25 m cells, 4 m window, k = 12 -- build, WIDE association,
-    solve (more than 1024 residual slots: the raw-slot walk of the pass) against the oracle."""
+    solve against the oracle.  (57 moving cells, 684 table slots, 613 residuals: the solve compacts them like any other
+    registration; the raw-slot walk of the pass is reached in test_gpu_solve_sizes.py.)"""
     torch, dev, ctx = env
     mapp_args = (200, 200, 0.25, 0.0, 0.0, 4.0, 3, 0)
     mapp, clu = R.MapParams(*mapp_args), R.ClusterParams(9216, 24.0)
