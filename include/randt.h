@@ -522,6 +522,39 @@ int randt_filter_build(randt_ctx* ctx, const float* h_raw, int n_azimuths, int n
                        const randt_filter_params* fp, const randt_cluster_params* cp, int max_points, randt_maps* out, int map_idx,
                        int* status);
 
+/* The same filter for scans delivered as azimuth x range intensity rasters -- what a scanning radar sends (400 x 3768 uint8 per
+ * revolution of a Navtech) -- instead of point clouds.  v(a, b) is the raster value of azimuth a, bin b; with cossin[a] =
+ * (c_a, s_a) and ranges[b] the EXPANSION of a raster is the packed x y z I cloud whose point a * n_bins + b is
+ *   x = ranges[b] * c_a,  y = ranges[b] * s_a,  z = 0,  I = (float)v(a, b) * intensity_scale      (one fp32 multiply each),
+ * and every raster entry returns exactly -- bit for bit, status included -- what its point-cloud twin returns on the expansion
+ * (stride_floats 4, intensity_index 3).  A uint8 raster is 1/16 of the expansion's bytes. */
+enum { RANDT_RASTER_U8 = 0, RANDT_RASTER_U16 = 1, RANDT_RASTER_F32 = 2 };
+typedef struct randt_polar_raster {
+  int32_t elem_type, n_azimuths, n_bins, reserved;
+  int64_t row_pitch_bytes, scan_pitch_bytes; /* >= n_bins * element size / >= n_azimuths * row_pitch_bytes */
+  float intensity_scale;
+  float reserved_f;
+} randt_polar_raster;
+/* n_scans rasters in device memory, scan s at d_raster + s * scan_pitch_bytes (16-byte aligned, row_pitch_bytes % 16 == 0 and
+ * scan_pitch_bytes % 16 == 0, otherwise RANDT_ERR_INVALID; bytes of a row beyond its n_bins values are never looked at);
+ * d_cossin = [n_scans][n_azimuths][2] floats, d_ranges = [n_bins] floats, shared by the scans.  Outputs and d_status as
+ * randt_filter_scan_batch_dev.  Enqueue-only. */
+int randt_filter_raster_batch_dev(randt_ctx* ctx, const void* d_raster, const randt_polar_raster* desc, const float* d_cossin,
+                                  const float* d_ranges, int n_scans, const randt_filter_params* fp, float* d_out_points,
+                                  int pitch_out, int32_t* d_out_counts, float* d_out_polar, float* d_peaks,
+                                  int32_t* d_peak_counts, int32_t* d_status);
+/* Host twins of randt_filter_scan / randt_filter_build for ONE raster in host memory (desc->scan_pitch_bytes is not used).  Any
+ * start address and any row pitch >= n_bins * element size are accepted -- h_raster may point behind a per-row header, as in
+ * the Oxford radar PNGs (11 metadata bytes, then 3768 values: h_raster = image + 11, row_pitch_bytes = 3779); the rows are
+ * repacked into an aligned device pitch by the upload.  h_cossin = [n_azimuths][2], h_ranges = [n_bins].  Synchronisation as
+ * the twins: the host buffers are free on return. */
+int randt_filter_raster(randt_ctx* ctx, const void* h_raster, const randt_polar_raster* desc, const float* h_cossin,
+                        const float* h_ranges, const randt_filter_params* fp, float* h_out_points, int capacity, int* n_out,
+                        float* h_out_polar, float* h_peaks, int* n_peaks, int* status);
+int randt_filter_raster_build(randt_ctx* ctx, const void* h_raster, const randt_polar_raster* desc, const float* h_cossin,
+                              const float* h_ranges, const randt_filter_params* fp, const randt_cluster_params* cp,
+                              int max_points, randt_maps* out, int map_idx, int* status);
+
 
 /* ------------------------------------------------------------------ fixed-lag window (a16, a17) */
 /* Matcher::predictTransform, optimize_on_manifold branch (ndt_matcher.cpp:22-59) with predictSE2

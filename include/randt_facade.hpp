@@ -609,15 +609,57 @@ class RadarPreprocessor {
   // intensity) of every flushed azimuth.  Returns false (outputs untouched) if the cloud is not azimuth-organised or the call failed.
   bool filterScan(const float* raw, int n_azimuths, int n_bins, int stride, int intensity_index, std::vector<float>& cloud_out,
                   std::vector<std::pair<double, double>>& polar_points, std::vector<std::array<double, 3>>& max_detections) const {
+    return filtered(static_cast<long long>(n_azimuths) * n_bins, n_azimuths, "randt_filter_scan", cloud_out, polar_points, max_detections,
+                    [&](float* pts, int capacity, int* n, float* pol, float* pk, int* npk, int* status) {
+                      return randt_filter_scan(ctx_->get(), raw, n_azimuths, n_bins, stride, intensity_index, &fp_, pts, capacity, n, pol, pk, npk, status);
+                    });
+  }
+  // RadarPreprocessor::processScan + HierarchicalMap::addClusters (local_fuser.cpp:102-105) without the host round trip of the
+  // filtered points: raw scan up, filter -> clustering -> NDT on the device into scan_ndt.  Returns the filter's status check.
+  bool processScan(const float* raw, int n_azimuths, int n_bins, int stride, int intensity_index, Map& scan_ndt, int max_points = 6144) const {
+    randt_cluster_params cp{clustering_.n_clusters, static_cast<float>(clustering_.max_range)};
+    int status = 0;
+    randt_maps* m = scan_ndt.mutable_handle();
+    if (!m || !facade_check(randt_filter_build(ctx_->get(), raw, n_azimuths, n_bins, stride, intensity_index, &fp_, &cp, max_points, m, 0, &status),
+                            "randt_filter_build", ctx_->get()))
+      return false;
+    return built("processScan", status);
+  }
+
+  // The two calls above for a scan delivered as an azimuth x range intensity raster (randt_polar_raster in randt.h: what the
+  // sensor sends, 1/16 of the cloud's bytes for uint8) with its tables cossin = [n_azimuths][2], ranges = [n_bins]; any host row
+  // pitch and start address.  Results, return values and warnings are filterScan's / processScan's on the expansion of the raster.
+  bool filterPolarRaster(const void* raster, const randt_polar_raster& desc, const float* cossin, const float* ranges, std::vector<float>& cloud_out,
+                         std::vector<std::pair<double, double>>& polar_points, std::vector<std::array<double, 3>>& max_detections) const {
+    return filtered(static_cast<long long>(desc.n_azimuths) * desc.n_bins, desc.n_azimuths, "randt_filter_raster", cloud_out, polar_points, max_detections,
+                    [&](float* pts, int capacity, int* n, float* pol, float* pk, int* npk, int* status) {
+                      return randt_filter_raster(ctx_->get(), raster, &desc, cossin, ranges, &fp_, pts, capacity, n, pol, pk, npk, status);
+                    });
+  }
+  bool processPolarRaster(const void* raster, const randt_polar_raster& desc, const float* cossin, const float* ranges, Map& scan_ndt,
+                          int max_points = 6144) const {
+    randt_cluster_params cp{clustering_.n_clusters, static_cast<float>(clustering_.max_range)};
+    int status = 0;
+    randt_maps* m = scan_ndt.mutable_handle();
+    if (!m || !facade_check(randt_filter_raster_build(ctx_->get(), raster, &desc, cossin, ranges, &fp_, &cp, max_points, m, 0, &status),
+                            "randt_filter_raster_build", ctx_->get()))
+      return false;
+    return built("processPolarRaster", status);
+  }
+
+ private:
+  // filterScan's host side for either input: `call` runs the filter into buffers of `capacity` points; more kept points than
+  // that: once more with a larger buffer; the outputs are only touched on success
+  template <class Call>
+  bool filtered(long long n_cloud, int n_azimuths, const char* what, std::vector<float>& cloud_out, std::vector<std::pair<double, double>>& polar_points,
+                std::vector<std::array<double, 3>>& max_detections, Call&& call) const {
     int capacity = 8192;
     for (;;) {
-      std::vector<float> pts(static_cast<size_t>(capacity) * 4), pol(static_cast<size_t>(capacity) * 2), pk(static_cast<size_t>(n_azimuths) * 3);
+      std::vector<float> pts(static_cast<size_t>(capacity) * 4), pol(static_cast<size_t>(capacity) * 2), pk(static_cast<size_t>(std::max(n_azimuths, 1)) * 3);
       int n = 0, npk = 0, status = 0;
-      if (!facade_check(randt_filter_scan(ctx_->get(), raw, n_azimuths, n_bins, stride, intensity_index, &fp_, pts.data(), capacity, &n, pol.data(), pk.data(),
-                                          &npk, &status), "randt_filter_scan", ctx_->get()))
-        return false;
-      if (status == 2 && capacity < n_azimuths * n_bins) {  // more kept points than the buffer: once more with a larger one
-        capacity = std::min(capacity * 4, n_azimuths * n_bins);
+      if (!facade_check(call(pts.data(), capacity, &n, pol.data(), pk.data(), &npk, &status), what, ctx_->get())) return false;
+      if (status == 2 && capacity < n_cloud) {
+        capacity = static_cast<int>(std::min<long long>(static_cast<long long>(capacity) * 4, n_cloud));
         continue;
       }
       if (status != 0) {
@@ -632,20 +674,11 @@ class RadarPreprocessor {
       return true;
     }
   }
-  // RadarPreprocessor::processScan + HierarchicalMap::addClusters (local_fuser.cpp:102-105) without the host round trip of the
-  // filtered points: raw scan up, filter -> clustering -> NDT on the device into scan_ndt.  Returns the filter's status check.
-  bool processScan(const float* raw, int n_azimuths, int n_bins, int stride, int intensity_index, Map& scan_ndt, int max_points = 6144) const {
-    randt_cluster_params cp{clustering_.n_clusters, static_cast<float>(clustering_.max_range)};
-    int status = 0;
-    randt_maps* m = scan_ndt.mutable_handle();
-    if (!m || !facade_check(randt_filter_build(ctx_->get(), raw, n_azimuths, n_bins, stride, intensity_index, &fp_, &cp, max_points, m, 0, &status),
-                            "randt_filter_build", ctx_->get()))
-      return false;
-    if (status != 0) std::cout << "WARNING: processScan: filter status " << status << (status == 2 ? " (more kept points than max_points)" : " (cloud not azimuth-organised)") << "\n";
+  // the filter's status after a filter -> clustering -> NDT call, with the caller's name in the warning
+  static bool built(const char* who, int status) {
+    if (status != 0) std::cout << "WARNING: " << who << ": filter status " << status << (status == 2 ? " (more kept points than max_points)" : " (cloud not azimuth-organised)") << "\n";
     return status == 0;
   }
-
- private:
   std::shared_ptr<Context> ctx_;
   RadarPreprocessorParameters clustering_;
   randt_filter_params fp_{};

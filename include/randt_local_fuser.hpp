@@ -342,10 +342,21 @@ class LocalFuser {
   // the same on a RAW polar scan (n_azimuths x n_bins points, azimuth after azimuth): RadarPreprocessor::processScan's filterScan
   // runs first (radar_preprocessor.cpp:45-125), on the device
   void processPolarScan(const float* raw, int n_azimuths, int n_bins, int stride, int intensity_index, double stamp, double imu_yaw_increment = 0.0) {
+    PolarSourceReset reset{this};  // also when processScan throws (ErrorPolicy kThrow)
     polar_az_ = n_azimuths;
     polar_bins_ = n_bins;
     processScan(raw, n_azimuths * n_bins, stride, intensity_index, stamp, kAddScan, imu_yaw_increment);
-    polar_az_ = polar_bins_ = 0;
+  }
+  // the same on a scan delivered as an azimuth x range intensity raster with its tables (RadarPreprocessor::filterPolarRaster /
+  // processPolarRaster): the poses are those of processPolarScan on the expansion of the raster
+  void processPolarRaster(const void* raster, const randt_polar_raster& desc, const float* cossin, const float* ranges, double stamp,
+                          double imu_yaw_increment = 0.0) {
+    PolarSourceReset reset{this};
+    raster_ = raster;
+    raster_desc_ = desc;
+    raster_cossin_ = cossin;
+    raster_ranges_ = ranges;
+    processScan(nullptr, 0, 4, 3, stamp, kAddScan, imu_yaw_increment);
   }
   // imu_yaw_increment: the heading change since the last scan from the IMU (what the reference extracts from the two orientation
   // quaternions, local_fuser.cpp:107-121; used when ndt_matcher_parameters.use_imu is set), 0 otherwise
@@ -354,7 +365,17 @@ class LocalFuser {
     yaw_ = imu_yaw_increment;
     HierarchicalMap current_scan;  // :103-105
     current_scan.initialize(ctx_, map_parameters_, 0.0, 0.0, parameters_.scan_cell_capacity);
-    if (polar_az_ > 0 && slam_) {
+    if (raster_ && slam_) {
+      std::vector<std::pair<double, double>> polar_detections;
+      std::vector<std::array<double, 3>> peak_detections;
+      if (_preprocessor.filterPolarRaster(raster_, raster_desc_, raster_cossin_, raster_ranges_, filtered_, polar_detections, peak_detections)) {
+        points = filtered_.data();
+        n_points = static_cast<int>(filtered_.size() / 4);
+        current_scan.addScan(points, n_points, stride, intensity_index, preprocessor_parameters_);
+      }
+    } else if (raster_) {
+      _preprocessor.processPolarRaster(raster_, raster_desc_, raster_cossin_, raster_ranges_, current_scan.getMap());
+    } else if (polar_az_ > 0 && slam_) {
       // the loop search wants the FILTERED cloud on the host (SCManager keys of a keyframe, local_fuser.cpp:207): filterScan's
       // outputs come back once, the scan's NDT is built from them
       std::vector<std::pair<double, double>> polar_detections;
@@ -527,6 +548,17 @@ class LocalFuser {
   Matcher ndt_matcher_;
   RadarPreprocessor _preprocessor;
   int polar_az_ = 0, polar_bins_ = 0;
+  struct PolarSourceReset {  // processScan takes a polar source from the members below: they never outlive the call that set them
+    LocalFuser* f;
+    ~PolarSourceReset() {
+      f->polar_az_ = f->polar_bins_ = 0;
+      f->raster_ = nullptr;
+      f->raster_cossin_ = f->raster_ranges_ = nullptr;
+    }
+  };
+  const void* raster_ = nullptr;  // processPolarRaster's scan while it is being processed
+  randt_polar_raster raster_desc_{};
+  const float *raster_cossin_ = nullptr, *raster_ranges_ = nullptr;
   Map _current_submap, _last_submap_transformed, _last_scan_kept, _last_merged_map;
   std::deque<Map> _map_window, _next_maps_to_insert;
   std::vector<float> clustered_, filtered_;

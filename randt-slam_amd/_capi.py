@@ -62,6 +62,15 @@ class FilterParams(C.Structure):
                 ("beam_distance_increment_threshold", C.c_float), ("sensor_to_base", C.c_float * 12)]
 
 
+RASTER_U8, RASTER_U16, RASTER_F32 = 0, 1, 2
+
+
+class PolarRaster(C.Structure):
+    """randt_polar_raster: layout of azimuth x range intensity rasters."""
+    _fields_ = [("elem_type", C.c_int32), ("n_azimuths", C.c_int32), ("n_bins", C.c_int32), ("reserved", C.c_int32),
+                ("row_pitch_bytes", C.c_int64), ("scan_pitch_bytes", C.c_int64), ("intensity_scale", C.c_float), ("reserved_f", C.c_float)]
+
+
 class ScParams(C.Structure):
     _fields_ = [("num_ring", C.c_int32), ("num_sector", C.c_int32), ("max_radius", C.c_double),
                 ("num_exclude_recent", C.c_int32), ("num_candidates", C.c_int32), ("search_ratio", C.c_double),
@@ -164,6 +173,9 @@ SYMBOLS = {
     "randt_filter_scan_batch_dev": (_I, [_V, _V, _I, _I, _I, _I, _I, _P(FilterParams), _V, _I, _V, _V, _V, _V, _V]),
     "randt_filter_scan": (_I, [_V, _V, _I, _I, _I, _I, _P(FilterParams), _V, _I, _P(_I), _V, _V, _P(_I), _P(_I)]),
     "randt_filter_build": (_I, [_V, _V, _I, _I, _I, _I, _P(FilterParams), _P(ClusterParams), _I, _V, _I, _P(_I)]),
+    "randt_filter_raster_batch_dev": (_I, [_V, _V, _P(PolarRaster), _V, _V, _I, _P(FilterParams), _V, _I, _V, _V, _V, _V, _V]),
+    "randt_filter_raster": (_I, [_V, _V, _P(PolarRaster), _V, _V, _P(FilterParams), _V, _I, _P(_I), _V, _V, _P(_I), _P(_I)]),
+    "randt_filter_raster_build": (_I, [_V, _V, _P(PolarRaster), _V, _V, _P(FilterParams), _P(ClusterParams), _I, _V, _I, _P(_I)]),
     "randt_sc_make_batch_dev": (_I, [_V, _V, _I, _I, _V, _I, _I, _P(ScParams), _V, _V, _V]),
     "randt_sc_detect_batch_dev": (_I, [_V, _P(ScParams), _V, _V, _V, _V, _I, _V, _I, _V, _V, _V]),
     "randt_sc_db_create": (_I, [_V, _P(ScParams), _I, _P(_V)]),

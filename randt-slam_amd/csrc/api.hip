@@ -1637,7 +1637,7 @@ int randt_filter_scan_batch_dev(randt_ctx* ctx, const float* d_raw, int n_scans,
   if (!d_raw || !d_out_points || !d_out_counts || !d_status) return RANDT_ERR_INVALID;
   if (stride_floats == 4 && ((size_t)d_raw & 15) != 0) return randt_set_error(ctx, RANDT_ERR_INVALID, "packed xyzI input must be 16-byte aligned", hipSuccess);
   if ((long long)n_azimuths * n_bins > (1ll << 30)) return RANDT_ERR_UNSUPPORTED;
-  int rc = randt_scratch_reserve(ctx, ctx->ws, (size_t)n_scans * n_azimuths * (32 + 4 * 2 * 16) + 512);  // row records + FILT_STAGE staged points per row (filter.hip)
+  int rc = randt_scratch_reserve(ctx, ctx->ws, (size_t)n_scans * n_azimuths * FILT_WS_PER_ROW + 512);
   if (rc) return rc;
   return launch_filter_scan(ctx, d_raw, n_scans, n_azimuths, n_bins, stride_floats, intensity_index, fp, d_out_points, pitch_out,
                             d_out_counts, d_out_polar, d_peaks, d_peak_counts, d_status, ctx->ws.p);
@@ -1673,6 +1673,25 @@ int filter_upload(randt_ctx* ctx, const float* h_raw, int n_az, int n_bins, int 
 }
 }  // namespace
 
+namespace {
+// results of one filtered scan back to the host: [count, peak count, status] first, then as many points / pairs / peaks
+int filter_readback(randt_ctx* ctx, const float* d_pts, const float* d_polar, const float* d_peaks, const int32_t* d_tail, float* h_out_points,
+                    int capacity, int* n_out, float* h_out_polar, float* h_peaks, int* n_peaks, int* status) {
+  int32_t h_tail[3] = {0, 0, 0};
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_tail, d_tail, sizeof(h_tail), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  const int n = h_tail[0] < capacity ? h_tail[0] : capacity;
+  if (n > 0) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_out_points, d_pts, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (n > 0 && h_out_polar) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_out_polar, d_polar, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (h_peaks && h_tail[1] > 0) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_peaks, d_peaks, sizeof(float) * 3 * (size_t)h_tail[1], hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  *n_out = h_tail[0];
+  if (n_peaks) *n_peaks = h_tail[1];
+  *status = h_tail[2];
+  return RANDT_OK;
+}
+}  // namespace
+
 int randt_filter_scan(randt_ctx* ctx, const float* h_raw, int n_azimuths, int n_bins, int stride_floats, int intensity_index,
                       const randt_filter_params* fp, float* h_out_points, int capacity, int* n_out, float* h_out_polar, float* h_peaks,
                       int* n_peaks, int* status) {
@@ -1686,18 +1705,7 @@ int randt_filter_scan(randt_ctx* ctx, const float* h_raw, int n_azimuths, int n_
   rc = randt_filter_scan_batch_dev(ctx, b.raw, 1, n_azimuths, n_bins, stride_floats, intensity_index, fp, b.pts, capacity, b.tail, b.polar, b.peaks,
                                    h_peaks ? b.tail + 1 : nullptr, b.tail + 2);
   if (rc) return drained(ctx, rc);
-  int32_t h_tail[3] = {0, 0, 0};
-  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_tail, b.tail, sizeof(h_tail), hipMemcpyDeviceToHost, ctx->stream));
-  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
-  const int n = h_tail[0] < capacity ? h_tail[0] : capacity;
-  if (n > 0) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_out_points, b.pts, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (n > 0 && h_out_polar) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_out_polar, b.polar, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (h_peaks && h_tail[1] > 0) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_peaks, b.peaks, sizeof(float) * 3 * (size_t)h_tail[1], hipMemcpyDeviceToHost, ctx->stream));
-  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
-  *n_out = h_tail[0];
-  if (n_peaks) *n_peaks = h_tail[1];
-  *status = h_tail[2];
-  return RANDT_OK;
+  return filter_readback(ctx, b.pts, b.polar, b.peaks, b.tail, h_out_points, capacity, n_out, h_out_polar, h_peaks, n_peaks, status);
 }
 
 int randt_filter_build(randt_ctx* ctx, const float* h_raw, int n_azimuths, int n_bins, int stride_floats, int intensity_index,
@@ -1711,6 +1719,115 @@ int randt_filter_build(randt_ctx* ctx, const float* h_raw, int n_azimuths, int n
   if (rc) return rc;
   rc = randt_filter_scan_batch_dev(ctx, b.raw, 1, n_azimuths, n_bins, stride_floats, intensity_index, fp, b.pts, max_points, b.tail, nullptr, nullptr,
                                    nullptr, b.tail + 2);
+  if (rc) return rc;
+  rc = randt_ndt_build_batch_dev(ctx, b.pts, 1, max_points, b.tail, 4, 3, cp, out, map_idx);
+  if (rc || !status) return rc;
+  int32_t h_status = 0;
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(&h_status, b.tail + 2, sizeof(h_status), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  *status = h_status;
+  return RANDT_OK;
+}
+
+// ---- the same filter on azimuth x range intensity rasters
+namespace {
+size_t raster_elem_size(int elem_type) { return elem_type == RANDT_RASTER_U8 ? 1 : (elem_type == RANDT_RASTER_U16 ? 2 : 4); }
+// what the host can see of a descriptor (the scan pitch only matters to the batch entry)
+bool raster_desc_ok(const randt_polar_raster* d, bool batch) {
+  if (!d || d->elem_type < RANDT_RASTER_U8 || d->elem_type > RANDT_RASTER_F32 || d->n_azimuths <= 0 || d->n_bins <= 0) return false;
+  if ((long long)d->n_azimuths * d->n_bins > (1ll << 30)) return false;
+  if (d->row_pitch_bytes < (int64_t)((size_t)d->n_bins * raster_elem_size(d->elem_type))) return false;
+  if (batch && d->scan_pitch_bytes / d->n_azimuths < d->row_pitch_bytes) return false;
+  return true;
+}
+}  // namespace
+
+int randt_filter_raster_batch_dev(randt_ctx* ctx, const void* d_raster, const randt_polar_raster* desc, const float* d_cossin,
+                                  const float* d_ranges, int n_scans, const randt_filter_params* fp, float* d_out_points, int pitch_out,
+                                  int32_t* d_out_counts, float* d_out_polar, float* d_peaks, int32_t* d_peak_counts, int32_t* d_status) {
+  DeviceGuard dev_guard__(ctx);
+  if (!ctx || !fp || !desc || n_scans < 0 || pitch_out <= 0) return RANDT_ERR_INVALID;
+  if (desc->n_azimuths > 0 && desc->n_bins > 0 && (long long)desc->n_azimuths * desc->n_bins > (1ll << 30)) return RANDT_ERR_UNSUPPORTED;
+  if (!raster_desc_ok(desc, true)) return randt_set_error(ctx, RANDT_ERR_INVALID, "polar raster: element type, sizes or pitches of the descriptor", hipSuccess);
+  if (n_scans == 0) return RANDT_OK;
+  if (!d_raster || !d_cossin || !d_ranges || !d_out_points || !d_out_counts || !d_status) return RANDT_ERR_INVALID;
+  if (((size_t)d_raster & 15) != 0 || (desc->row_pitch_bytes & 15) != 0 || (desc->scan_pitch_bytes & 15) != 0)
+    return randt_set_error(ctx, RANDT_ERR_INVALID, "polar raster: device raster, row pitch and scan pitch must be multiples of 16 bytes", hipSuccess);
+  if (((size_t)d_cossin & 3) != 0 || ((size_t)d_ranges & 3) != 0) return RANDT_ERR_INVALID;
+  int rc = randt_scratch_reserve(ctx, ctx->ws, (size_t)n_scans * desc->n_azimuths * FILT_WS_PER_ROW + 512);
+  if (rc) return rc;
+  return launch_filter_raster(ctx, d_raster, desc, d_cossin, d_ranges, n_scans, fp, d_out_points, pitch_out, d_out_counts, d_out_polar, d_peaks,
+                              d_peak_counts, d_status, ctx->ws.p);
+}
+
+// one raster and its tables from the host into a pooled device block [raster | cossin | ranges | points | polar | peaks | tail]
+namespace {
+struct RasterBlock {
+  PooledBlock blk;
+  unsigned char* ras = nullptr;
+  float *cossin = nullptr, *ranges = nullptr, *pts = nullptr, *polar = nullptr, *peaks = nullptr;
+  int32_t* tail = nullptr;  // [0] count, [1] peak count, [2] status
+  randt_polar_raster dev;   // the descriptor of the device copy: rows repacked to a pitch that is a multiple of 16
+  explicit RasterBlock(randt_ctx* ctx) : blk(ctx) {}
+  void carve(Carve& c, const randt_polar_raster& d, int capacity, bool want_polar, bool want_peaks) {
+    dev = d;
+    dev.row_pitch_bytes = (int64_t)(((size_t)d.n_bins * raster_elem_size(d.elem_type) + 15) & ~(size_t)15);
+    dev.scan_pitch_bytes = dev.row_pitch_bytes * d.n_azimuths;
+    ras = c.take<unsigned char>((size_t)dev.scan_pitch_bytes);
+    cossin = c.take<float>(2 * (size_t)d.n_azimuths);
+    ranges = c.take<float>((size_t)d.n_bins);
+    pts = c.take<float>(4 * (size_t)capacity);
+    polar = want_polar ? c.take<float>(2 * (size_t)capacity) : nullptr;
+    peaks = want_peaks ? c.take<float>(3 * (size_t)d.n_azimuths) : nullptr;
+    tail = c.take<int32_t>(3);
+  }
+};
+int raster_upload(randt_ctx* ctx, const void* h_raster, const randt_polar_raster* desc, const float* h_cossin, const float* h_ranges, int capacity,
+                  bool want_polar, bool want_peaks, RasterBlock* b) {
+  const hipError_t e = b->blk.alloc(carved_size([&](Carve& c) { b->carve(c, *desc, capacity, want_polar, want_peaks); }));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    b->blk.p = nullptr;
+    return randt_set_error(ctx, e == hipErrorOutOfMemory ? RANDT_ERR_NOMEM : RANDT_ERR_HIP, "hipMalloc (polar raster)", e);
+  }
+  Carve c(b->blk.p);
+  b->carve(c, *desc, capacity, want_polar, want_peaks);
+  // any host pitch and start address: the 2-D copy repacks the rows (their n_bins values only) into the aligned device pitch
+  RANDT_HIP_CHECK(ctx, hipMemcpy2DAsync(b->ras, (size_t)b->dev.row_pitch_bytes, h_raster, (size_t)desc->row_pitch_bytes,
+                                        (size_t)desc->n_bins * raster_elem_size(desc->elem_type), (size_t)desc->n_azimuths, hipMemcpyHostToDevice,
+                                        ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(b->cossin, h_cossin, sizeof(float) * 2 * (size_t)desc->n_azimuths, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(b->ranges, h_ranges, sizeof(float) * (size_t)desc->n_bins, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));  // the caller's buffers (pageable or pinned) are free on return
+  return RANDT_OK;
+}
+}  // namespace
+
+int randt_filter_raster(randt_ctx* ctx, const void* h_raster, const randt_polar_raster* desc, const float* h_cossin, const float* h_ranges,
+                        const randt_filter_params* fp, float* h_out_points, int capacity, int* n_out, float* h_out_polar, float* h_peaks,
+                        int* n_peaks, int* status) {
+  DeviceGuard dev_guard__(ctx);
+  if (!ctx || !fp || !h_raster || !h_cossin || !h_ranges || !h_out_points || !n_out || !status || capacity <= 0 || !raster_desc_ok(desc, false))
+    return RANDT_ERR_INVALID;
+  RasterBlock b(ctx);
+  int rc = raster_upload(ctx, h_raster, desc, h_cossin, h_ranges, capacity, h_out_polar != nullptr, h_peaks != nullptr, &b);
+  if (rc) return rc;
+  rc = randt_filter_raster_batch_dev(ctx, b.ras, &b.dev, b.cossin, b.ranges, 1, fp, b.pts, capacity, b.tail, b.polar, b.peaks,
+                                     h_peaks ? b.tail + 1 : nullptr, b.tail + 2);
+  if (rc) return drained(ctx, rc);
+  return filter_readback(ctx, b.pts, b.polar, b.peaks, b.tail, h_out_points, capacity, n_out, h_out_polar, h_peaks, n_peaks, status);
+}
+
+int randt_filter_raster_build(randt_ctx* ctx, const void* h_raster, const randt_polar_raster* desc, const float* h_cossin, const float* h_ranges,
+                              const randt_filter_params* fp, const randt_cluster_params* cp, int max_points, randt_maps* out, int map_idx,
+                              int* status) {
+  DeviceGuard dev_guard__(ctx);
+  if (!ctx || !fp || !cp || !h_raster || !h_cossin || !h_ranges || !range_ok(out, map_idx, 1) || max_points <= 0 || !raster_desc_ok(desc, false))
+    return RANDT_ERR_INVALID;
+  RasterBlock b(ctx);  // parked again at scope exit: whatever reuses it is enqueued behind the kernels
+  int rc = raster_upload(ctx, h_raster, desc, h_cossin, h_ranges, max_points, false, false, &b);
+  if (rc) return rc;
+  rc = randt_filter_raster_batch_dev(ctx, b.ras, &b.dev, b.cossin, b.ranges, 1, fp, b.pts, max_points, b.tail, nullptr, nullptr, nullptr, b.tail + 2);
   if (rc) return rc;
   rc = randt_ndt_build_batch_dev(ctx, b.pts, 1, max_points, b.tail, 4, 3, cp, out, map_idx);
   if (rc || !status) return rc;

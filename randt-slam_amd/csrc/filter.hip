@@ -87,19 +87,55 @@ struct FilterArgs {
   // scratch
   RowRec* rows;       // [n_scans][n_az]
   float4* stage;      // [n_scans][n_az][FILT_STAGE][2]: {x' y' z' I}, {atan2 range - -} of a row's first kept points
+  // SRC_RASTER only: the scan as an azimuth x range intensity raster and its two tables (raw is null then)
+  const unsigned char* raster;  // [n_scans] scan_pitch bytes, rows of row_pitch bytes (16-byte aligned, pitch % 16 == 0)
+  const float* cossin;          // [n_scans][n_az][2]
+  const float* ranges;          // [n_bins]
+  long long row_pitch, scan_pitch;
+  float iscale;
+  int elem;                     // RANDT_RASTER_U8 / U16 / F32
+  int rng_vec;                  // ranges is 16-byte aligned
 };
 
-// PACKED: 16-byte x y z I records (one dwordx4 load per point), known at compile time so that a row's loads are
-// issued back to back with no branch between them.
-template <bool PACKED>
-__device__ __forceinline__ void fetch(const FilterArgs& A, const float* base, long long i, float& x, float& y, float& in) {
-  if (PACKED) {
-    const float4 p = reinterpret_cast<const float4*>(base)[i];
+// Where a kernel finds the points of a scan.  SRC_PACKED: 16-byte x y z I records (one dwordx4 load per point), known at
+// compile time so that a row's loads are issued back to back with no branch between them; SRC_STRIDED: records of A.stride
+// floats; SRC_RASTER: one intensity per bin, the point is formed from the tables -- x = ranges[b] * c_a, y = ranges[b] * s_a,
+// z = 0, I = (float)v * iscale, one fp32 multiply each: what a converter would have written into the packed cloud.
+enum { SRC_STRIDED = 0, SRC_PACKED = 1, SRC_RASTER = 2 };
+struct ScanSrc {
+  const float* base;          // cloud sources: the scan's first record
+  const unsigned char* ras;   // SRC_RASTER: the scan's first row
+  const float* cs;            //             the scan's (cos, sin) per azimuth
+};
+template <int SRC>
+__device__ __forceinline__ ScanSrc scan_src(const FilterArgs& A, int scan) {
+  ScanSrc S;
+  S.base = SRC == SRC_RASTER ? nullptr : A.raw + (size_t)scan * A.n_az * A.n_bins * A.stride;
+  S.ras = SRC == SRC_RASTER ? A.raster + (size_t)scan * A.scan_pitch : nullptr;
+  S.cs = SRC == SRC_RASTER ? A.cossin + (size_t)scan * A.n_az * 2 : nullptr;
+  return S;
+}
+
+// point i (cloud index within the scan, < 2^30) of a scan
+template <int SRC>
+__device__ __forceinline__ void fetch(const FilterArgs& A, const ScanSrc& S, long long i, float& x, float& y, float& in) {
+  if (SRC == SRC_PACKED) {
+    const float4 p = reinterpret_cast<const float4*>(S.base)[i];
     x = p.x;
     y = p.y;
     in = A.ioff == 3 ? p.w : (A.ioff == 2 ? p.z : (A.ioff == 1 ? p.y : p.x));
+  } else if (SRC == SRC_RASTER) {
+    const unsigned a = (unsigned)i / (unsigned)A.n_bins, b = (unsigned)i - a * (unsigned)A.n_bins;
+    const float r = A.ranges[b];
+    x = r * S.cs[2 * a];
+    y = r * S.cs[2 * a + 1];
+    const unsigned char* row = S.ras + (size_t)a * A.row_pitch;
+    const float v = A.elem == RANDT_RASTER_U8 ? (float)row[b]
+                                              : (A.elem == RANDT_RASTER_U16 ? (float)reinterpret_cast<const unsigned short*>(row)[b]
+                                                                            : reinterpret_cast<const float*>(row)[b]);
+    in = v * A.iscale;
   } else {
-    const float* p = base + (size_t)i * A.stride;
+    const float* p = S.base + (size_t)i * A.stride;
     x = p[0];
     y = p[1];
     in = p[A.ioff];
@@ -143,15 +179,16 @@ __device__ __forceinline__ float4 to_base(const FilterArgs& A, float x, float y,
   o.w = in;
   return o;
 }
-template <bool PACKED>
-__device__ __forceinline__ float fetch_z(const FilterArgs& A, const float* base, long long i) {
-  return PACKED ? reinterpret_cast<const float4*>(base)[i].z : (A.stride > 2 ? base[(size_t)i * A.stride + 2] : 0.f);
+template <int SRC>
+__device__ __forceinline__ float fetch_z(const FilterArgs& A, const ScanSrc& S, long long i) {
+  if (SRC == SRC_RASTER) return 0.f;
+  return SRC == SRC_PACKED ? reinterpret_cast<const float4*>(S.base)[i].z : (A.stride > 2 ? S.base[(size_t)i * A.stride + 2] : 0.f);
 }
-template <bool PACKED>
+template <int SRC>
 __global__ __launch_bounds__(FILT_EBLOCK) void k_filter_emit(FilterArgs A) {
   __shared__ unsigned long long scratch[FILT_EBLOCK / 64];
   const int scan = blockIdx.x, tid = threadIdx.x;
-  const float* base = A.raw + (size_t)scan * A.n_az * A.n_bins * A.stride;
+  const ScanSrc S = scan_src<SRC>(A, scan);
   const RowRec* rows = A.rows + (size_t)scan * A.n_az;
   int bad = 0;
   int n_det = 0, n_out = 0;
@@ -229,8 +266,8 @@ __global__ __launch_bounds__(FILT_EBLOCK) void k_filter_emit(FilterArgs A) {
             const long long j = j0 + u;
             x[u] = y[u] = in[u] = z[u] = 0.f;
             if (j <= rec.further) {
-              fetch<PACKED>(A, base, j, x[u], y[u], in[u]);
-              z[u] = fetch_z<PACKED>(A, base, j);
+              fetch<SRC>(A, S, j, x[u], y[u], in[u]);
+              z[u] = fetch_z<SRC>(A, S, j);
             }
           }
 #pragma unroll
@@ -261,8 +298,8 @@ __global__ __launch_bounds__(FILT_EBLOCK) void k_filter_emit(FilterArgs A) {
 // kept points per azimuth in the Oxford-shaped scans).
 // kept: how many bins of the walked parts (d = 0 .. stop inwards, d = 1 .. stop outwards, so that the detection itself
 // is counted once) pass the output thresholds (:110-118) -- the same loads serve both questions.
-template <bool PACKED>
-__device__ __forceinline__ bool expand_both(const FilterArgs& A, const float* base, long long n, long long m, int lane, long long& closer, long long& further,
+template <int SRC>
+__device__ __forceinline__ bool expand_both(const FilterArgs& A, const ScanSrc& S, long long n, long long m, int lane, long long& closer, long long& further,
                                             int& kept, float& range_m, float4* stage) {
   const int half = lane >> 5, l = lane & 31;
   const long long dir = half ? 1 : -1;
@@ -278,8 +315,8 @@ __device__ __forceinline__ bool expand_both(const FilterArgs& A, const float* ba
     float ha = 0.f, ax = 0.f, ay = 0.f, ai = 0.f;
     if (a_in) {
       float bx = 0.f, by = 0.f, bi = 0.f;
-      fetch<PACKED>(A, base, a, ax, ay, ai);
-      if (b_in) fetch<PACKED>(A, base, b, bx, by, bi);
+      fetch<SRC>(A, S, a, ax, ay, ai);
+      if (b_in) fetch<SRC>(A, S, b, bx, by, bi);
       keep = keep_point(A, ax, ay, ai, ha) && (half == 0 || d0 + l > 0);  // the detection itself is counted once (inward half)
       if (b_in) stop = ((double)(ha - hypot_f(bx, by)) > (double)A.thr) || (ai <= bi) || ((double)ha < (double)A.min_d);
     }
@@ -316,12 +353,92 @@ __device__ __forceinline__ bool expand_both(const FilterArgs& A, const float* ba
       const bool mine = half ? ((vf >> l) & 1u) : ((vc >> l) & 1u);
       if (mine) {
         const int rank = half ? __popc(vc) + __popc(vf & ((1u << l) - 1u)) : __popc(l == 31 ? 0u : (vc >> (l + 1)));
-        stage[2 * rank] = to_base(A, ax, ay, fetch_z<PACKED>(A, base, a), ai);
+        stage[2 * rank] = to_base(A, ax, ay, fetch_z<SRC>(A, S, a), ai);
         if (A.out_polar) stage[2 * rank + 1] = make_float4(atan2f(ay, ax), ha, 0.f, 0.f);
       }
     }
   }
   return staged;
+}
+
+// The per-point steps of a row kernel, shared by the cloud and the raster row kernels.  The kernels must stay on the HBM
+// roofline, so the two per-point tests are restated without transcendental work: (a) range: hypot() in float after a double
+// sqrt is monotone in d2 = x^2 + y^2, so the launcher bisects the two double thresholds once; (b) organisation: a point whose
+// direction is within 4e-5 rad of the row's first point (|cross| <= 4e-5 dot, dot > 0) cannot differ from it by 1e-4 in atan2f;
+// only other points (none in an organised scan) and rows next to the +-pi cut take the exact atan2f comparison (exact_change).
+struct RowWalk {
+  float x0, y0;        // the row's first point: its angle is the reference's current_angle for this azimuth
+  float best_i;        // max_intensity starts at 0: only intensity > 0 can win
+  int best_idx;
+  bool suspect;
+  __device__ __forceinline__ RowWalk(float x, float y) : x0(x), y0(y), best_i(0.f), best_idx(0x7fffffff), suspect(false) {}
+  // |atan2f(y0, x0)| >= 3.14, decided without the atan2f (a superset: tan(pi - 3.14) = 0.00159)
+  __device__ __forceinline__ bool near_cut() const { return x0 < 0.f && fabsf(y0) <= 0.002f * fabsf(x0); }
+  // (dot > 0: a zero-filled return passes 0 <= 0, but the reference's atan2(0, 0) = 0 starts a new azimuth there)
+  __device__ __forceinline__ bool off_direction(float px, float py) const {
+    const float cross = x0 * py - y0 * px, dot = x0 * px + y0 * py;
+    return !(fabsf(cross) <= 4e-5f * dot) || !(dot > 0.f);
+  }
+  __device__ __forceinline__ void visit(const FilterArgs& A, int b, float px, float py, float pin) {
+    suspect |= off_direction(px, py);
+    const double d2 = (double)px * (double)px + (double)py * (double)py;
+    if (d2 >= A.lo2 && d2 <= A.hi2) {
+      if (pin > best_i) {  // a lane meets its bins in increasing order: strict '>' keeps the first
+        best_i = pin;
+        best_idx = b;
+      }
+    }
+  }
+  // arg-max over the wavefront: larger intensity wins, ties -> smaller index (strict '>', first index wins)
+  __device__ __forceinline__ void reduce_wave() {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float oi = __shfl_xor(best_i, off, 64);
+      const int ox = __shfl_xor(best_idx, off, 64);
+      if (oi > best_i || (oi == best_i && ox < best_idx)) {
+        best_i = oi;
+        best_idx = ox;
+      }
+    }
+  }
+  // the exact organisation test of one point of a flagged row (a0 = atan2f(y0, x0), cut = !(|a0| < 3.14)): an azimuth change
+  // inside the row as the reference sees it
+  __device__ __forceinline__ bool exact_change(float a0, bool cut, float px, float py) const {
+    return (cut || off_direction(px, py)) && fabsf(atan2f(py, px) - a0) > 0.0001;
+  }
+};
+
+// What one wavefront does with its row's arg-max: the detection (with the reference's quirks), the run around it and the
+// 32-byte row record.  Shared by the cloud and the raster row kernels.
+template <int SRC>
+__device__ __forceinline__ void finish_row(const FilterArgs& A, const ScanSrc& S, long long g, int row, float best_i, int best_idx, float a0, int bad, int lane) {
+  const long long n = (long long)A.n_az * A.n_bins, r0 = (long long)row * A.n_bins;
+  // the row's detection; quirk: the first boundary pushes current_max_idx = 0 even if azimuth 0 had no valid return;
+  // the last azimuth is never flushed
+  long long m = (best_i > 0.f && best_idx != 0x7fffffff) ? r0 + best_idx : -1;
+  float pk_i = best_i;
+  if (row == 0 && m < 0) {
+    m = 0;
+    pk_i = 0.f;
+  }
+  if (row == A.n_az - 1) m = -1;
+  long long closer = 0, further = -1;
+  int kept = 0;
+  float range_m = 0.f;
+  bool staged = false;
+  if (m >= 0) staged = expand_both<SRC>(A, S, n, m, lane, closer, further, kept, range_m, A.stage + (size_t)g * (2 * FILT_STAGE));  // uniform over the wavefront
+  if (lane == 0) {
+    RowRec rec;
+    rec.m = (int32_t)m;
+    rec.closer = (int32_t)closer;
+    rec.further = (int32_t)further;
+    rec.kept = kept;
+    rec.angle = a0;
+    rec.maxi = pk_i;
+    rec.peak_range = range_m;
+    rec.bad = (bad ? 1 : 0) | (staged ? 2 : 0);
+    A.rows[g] = rec;
+  }
 }
 
 // One 256-thread WORKGROUP per azimuth row (round 5).  The whole row -- up to FILT_UNROLL x 256 = 3072 bins, 48 KB -- is in
@@ -350,34 +467,14 @@ __global__ __launch_bounds__(FILT_BLOCK) FILT_OCC void k_filter_rows(FilterArgs 
   const long long g = blockIdx.x;  // scan * n_az + row
   const int scan = (int)(g / A.n_az), row = (int)(g - (long long)scan * A.n_az);
   const float* base = A.raw + (size_t)scan * A.n_az * A.n_bins * A.stride;
-  const long long n = (long long)A.n_az * A.n_bins, r0 = (long long)row * A.n_bins;
+  const long long r0 = (long long)row * A.n_bins;
   const unsigned rec = PACKED ? 16u : 4u * (unsigned)A.stride;          // bytes per point
   const char* rb = reinterpret_cast<const char*>(base + r0 * A.stride);  // uniform; lane offsets within a row fit 32 bits
 
-  float best_i = 0.f;  // max_intensity starts at 0: only intensity > 0 can win
-  int best_idx = 0x7fffffff;
-  // the row's first point: its angle is the reference's current_angle for this azimuth (a uniform address: one scalar load)
+  // the row's first point (a uniform address: one scalar load)
   const float x0 = reinterpret_cast<const float*>(rb)[0], y0 = reinterpret_cast<const float*>(rb)[1];
-  // The kernel must stay on the HBM roofline, so the two per-point tests are restated without transcendental
-  // work: (a) range: hypot() in float after a double sqrt is monotone in d2 = x^2 + y^2, so the launcher
-  // bisects the two double thresholds once; (b) organisation: a point whose direction is within 4e-5 rad of
-  // the row's first point (|cross| <= 4e-5 dot, dot > 0) cannot differ from it by 1e-4 in atan2f; only other points
-  // (none in an organised scan) and rows next to the +-pi cut take the exact atan2f comparison (below).
-  // near_cut: |atan2f(y0, x0)| >= 3.14, decided without the atan2f (a superset: tan(pi - 3.14) = 0.00159)
-  const bool near_cut = x0 < 0.f && fabsf(y0) <= 0.002f * fabsf(x0);
-  bool suspect = false;
-  auto visit = [&](int b, float px, float py, float pin) {
-    const float cross = x0 * py - y0 * px, dot = x0 * px + y0 * py;
-    // (dot > 0: a zero-filled return passes 0 <= 0, but the reference's atan2(0, 0) = 0 starts a new azimuth there)
-    suspect |= !(fabsf(cross) <= 4e-5f * dot) || !(dot > 0.f);
-    const double d2 = (double)px * (double)px + (double)py * (double)py;
-    if (d2 >= A.lo2 && d2 <= A.hi2) {
-      if (pin > best_i) {  // a lane meets its bins in increasing order: strict '>' keeps the first
-        best_i = pin;
-        best_idx = b;
-      }
-    }
-  };
+  RowWalk W(x0, y0);
+  const bool near_cut = W.near_cut();
   // lane t holds bins t, t + 256, ...: FILT_UNROLL loads per lane and round, all issued before the first is looked at (rows
   // beyond 3072 bins take further rounds)
   for (int c0 = 0; c0 < A.n_bins; c0 += FILT_UNROLL * FILT_BLOCK) {
@@ -399,20 +496,13 @@ __global__ __launch_bounds__(FILT_BLOCK) FILT_OCC void k_filter_rows(FilterArgs 
     for (int u = 0; u < FILT_UNROLL; ++u) {
       const int b = c0 + u * FILT_BLOCK + tid;
       if (PACKED) asm volatile("" ::"v"(pt[u].z));  // keeps the record ONE dwordx4 load (z is not needed here: the compiler would split it in two)
-      if (b < A.n_bins) visit(b, pt[u].x, pt[u].y, (!PACKED || I3) ? pt[u].w : (A.ioff == 2 ? pt[u].z : (A.ioff == 1 ? pt[u].y : pt[u].x)));
+      if (b < A.n_bins) W.visit(A, b, pt[u].x, pt[u].y, (!PACKED || I3) ? pt[u].w : (A.ioff == 2 ? pt[u].z : (A.ioff == 1 ? pt[u].y : pt[u].x)));
     }
   }
-  // arg-max over the wavefront: larger intensity wins, ties -> smaller index (strict '>', first index wins)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float oi = __shfl_xor(best_i, off, 64);
-    const int ox = __shfl_xor(best_idx, off, 64);
-    if (oi > best_i || (oi == best_i && ox < best_idx)) {
-      best_i = oi;
-      best_idx = ox;
-    }
-  }
-  const int flagged = __ballot(suspect) != 0ull ? 1 : 0;
+  W.reduce_wave();
+  float best_i = W.best_i;
+  int best_idx = W.best_idx;
+  const int flagged = __ballot(W.suspect) != 0ull ? 1 : 0;
   if (lane == 0) {
     s_best[wave] = best_i;
     s_idx[wave] = best_idx;
@@ -447,44 +537,91 @@ __global__ __launch_bounds__(FILT_BLOCK) FILT_OCC void k_filter_rows(FilterArgs 
         qy[u] = q[1];
       }
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const float cross = x0 * qy[u] - y0 * qx[u], dot = x0 * qx[u] + y0 * qy[u];
-        if (c0 + u * FILT_BLOCK + tid < A.n_bins && (cut || !(fabsf(cross) <= 4e-5f * dot) || !(dot > 0.f))) {
-          const float ang = atan2f(qy[u], qx[u]);
-          if (fabsf(ang - a0) > 0.0001) bad = 1;  // an azimuth change inside the row
-        }
-      }
+      for (int u = 0; u < 8; ++u)
+        if (c0 + u * FILT_BLOCK + tid < A.n_bins && W.exact_change(a0, cut, qx[u], qy[u])) bad = 1;
     }
     bad = __syncthreads_or(bad);
   }
   if (wave != 0) return;
   if (!(any_flag || near_cut)) a0 = atan2f(y0, x0);
-  // the row's detection; quirk: the first boundary pushes current_max_idx = 0 even if azimuth 0 had no valid return;
-  // the last azimuth is never flushed
-  long long m = (best_i > 0.f && best_idx != 0x7fffffff) ? r0 + best_idx : -1;
-  float pk_i = best_i;
-  if (row == 0 && m < 0) {
-    m = 0;
-    pk_i = 0.f;
+  finish_row<PACKED ? SRC_PACKED : SRC_STRIDED>(A, scan_src<PACKED ? SRC_PACKED : SRC_STRIDED>(A, scan), g, row, best_i, best_idx, a0, bad, lane);
+}
+
+// The row kernel of a RASTER scan: ONE WAVEFRONT per azimuth row, 16 bytes of the raster per lane and load = 16 / 8 / 4 bins
+// for u8 / u16 / f32 (ELEM: the RANDT_RASTER_* code).  A Navtech row (3768 u8 bins) is four loads of the wavefront and a whole
+// scan 1.5 MB, so a launch is a chain of dependent rounds, not a stream: the raster loads of a round and the loads of the bins'
+// ranges (a 15 KB table that every row shares, so it lives in the caches; independent of the raster values) are all issued
+// before the first is looked at, the row's (cos, sin) is two scalars, and no barrier or LDS is needed -- the wavefront that found
+// the arg-max expands the run itself.  The per-bin steps are k_filter_rows's, on x = ranges[b] * c, y = ranges[b] * s and
+// I = (float)v * iscale: a lane meets its bins in increasing order (strict '>' keeps the first), lanes are combined towards the
+// smaller index.  Bins past n_bins inside the last 16 bytes of a pitched row are loaded (the pitch is a multiple of 16, so the
+// load stays inside the row) and never looked at.
+// Measured against the cloud kernels on the expansion (400 x 3768 u8, profiles/r07_polar_raster_probe.json): 59.6 against 71.2 us
+// per 16 scans, but 17.4 against 14.1 us for ONE scan per launch -- neither bytes nor the per-bin arithmetic bound it
+// (profiles/experiments/r07_filter_raster_geometry.md: what was tried, and what is open).
+#define FILT_RBLOCK 64
+template <int ELEM>
+__global__ __launch_bounds__(FILT_RBLOCK) void k_filter_raster_rows(FilterArgs A) {
+  constexpr int ESZ = ELEM == RANDT_RASTER_U8 ? 1 : (ELEM == RANDT_RASTER_U16 ? 2 : 4);
+  constexpr int EPL = 16 / ESZ;                            // bins per lane and load
+  constexpr int RU = ELEM == RANDT_RASTER_U8 ? 4 : 8;      // loads per lane and round
+  const int lane = threadIdx.x;
+  const long long g = blockIdx.x;  // scan * n_az + row
+  const int scan = (int)(g / A.n_az), row = (int)(g - (long long)scan * A.n_az);
+  const ScanSrc S = scan_src<SRC_RASTER>(A, scan);
+  const unsigned char* rb = S.ras + (size_t)row * A.row_pitch;  // uniform
+  const float c = S.cs[2 * row], s = S.cs[2 * row + 1];
+  const float* __restrict__ rng = A.ranges;
+  const int nb = A.n_bins;
+
+  // the row's first point, as the cloud path reads it from the expansion
+  const float x0 = rng[0] * c, y0 = rng[0] * s;
+  RowWalk W(x0, y0);
+  for (int c0 = 0; c0 < nb; c0 += RU * FILT_RBLOCK * EPL) {
+    uint4 q[RU];
+    float rg[RU][EPL];
+#pragma unroll
+    for (int u = 0; u < RU; ++u) {
+      const int b0 = c0 + (u * FILT_RBLOCK + lane) * EPL;
+      // a load that starts past the row re-reads the row's first 16 bytes and is skipped when visited
+      q[u] = *reinterpret_cast<const uint4*>(rb + (b0 < nb ? (size_t)b0 * ESZ : (size_t)0));
+#pragma unroll
+      for (int k = 0; k < EPL; k += 4) {
+        const int b = b0 + k;
+        if (A.rng_vec && b + 3 < nb) {
+          const float4 r4 = *reinterpret_cast<const float4*>(rng + b);
+          rg[u][k] = r4.x, rg[u][k + 1] = r4.y, rg[u][k + 2] = r4.z, rg[u][k + 3] = r4.w;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) rg[u][k + e] = rng[b + e < nb ? b + e : nb - 1];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < RU; ++u) {
+      const int b0 = c0 + (u * FILT_RBLOCK + lane) * EPL;
+      const unsigned w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+#pragma unroll
+      for (int k = 0; k < EPL; ++k) {
+        float v;
+        if (ELEM == RANDT_RASTER_U8) v = (float)((w[k >> 2] >> (8 * (k & 3))) & 0xffu);
+        else if (ELEM == RANDT_RASTER_U16) v = (float)((w[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+        else v = __uint_as_float(w[k]);
+        if (b0 + k < nb) W.visit(A, b0 + k, rg[u][k] * c, rg[u][k] * s, v * A.iscale);
+      }
+    }
   }
-  if (row == A.n_az - 1) m = -1;
-  long long closer = 0, further = -1;
-  int kept = 0;
-  float range_m = 0.f;
-  bool staged = false;
-  if (m >= 0) staged = expand_both<PACKED>(A, base, n, m, lane, closer, further, kept, range_m, A.stage + (size_t)g * (2 * FILT_STAGE));  // uniform over the wavefront
-  if (lane == 0) {
-    RowRec rec;
-    rec.m = (int32_t)m;
-    rec.closer = (int32_t)closer;
-    rec.further = (int32_t)further;
-    rec.kept = kept;
-    rec.angle = a0;
-    rec.maxi = pk_i;
-    rec.peak_range = range_m;
-    rec.bad = (bad ? 1 : 0) | (staged ? 2 : 0);
-    A.rows[g] = rec;
+  W.reduce_wave();
+  int bad = 0;
+  const float a0 = atan2f(y0, x0);
+  if (__ballot(W.suspect) != 0ull || W.near_cut()) {  // uniform over the wavefront
+    // the exact organisation test (the tables alone decide it: the raster is not read again)
+    const bool cut = !(fabsf(a0) < 3.14f);
+    for (int b = lane; b < nb; b += FILT_RBLOCK)
+      if (W.exact_change(a0, cut, rng[b] * c, rng[b] * s)) bad = 1;
+    bad = __ballot(bad != 0) != 0ull ? 1 : 0;
   }
+  finish_row<SRC_RASTER>(A, S, g, row, W.best_i, W.best_idx, a0, bad, lane);
 }
 
 }  // namespace
@@ -510,17 +647,14 @@ double first_true(Pred pred) {
 }
 }  // namespace
 
-int launch_filter_scan(randt_ctx* ctx, const float* d_raw, int n_scans, int n_az, int n_bins, int stride, int ioff,
-                       const randt_filter_params* fp, float* d_out_pts, int pitch_out, int32_t* d_out_counts, float* d_polar,
-                       float* d_peaks, int32_t* d_peak_counts, int32_t* d_status, void* d_scratch) {
-  randt_note_enqueue(ctx);  // (RANDT_SOLVE_AUTO of the process's other contexts: this one has work in flight)
-  FilterArgs A;
-  A.raw = d_raw;
+namespace {
+// everything of the kernels' arguments that does not depend on where the points come from
+int filter_args(randt_ctx* ctx, FilterArgs& A, int n_scans, int n_az, int n_bins, const randt_filter_params* fp, float* d_out_pts, int pitch_out,
+                int32_t* d_out_counts, float* d_polar, float* d_peaks, int32_t* d_peak_counts, int32_t* d_status, void* d_scratch) {
+  memset(&A, 0, sizeof(A));
   A.n_scans = n_scans;
   A.n_az = n_az;
   A.n_bins = n_bins;
-  A.stride = stride;
-  A.ioff = ioff;
   A.min_d = fp->min_range;
   A.max_d = fp->max_range;
   A.min_i = fp->min_intensity;
@@ -543,19 +677,62 @@ int launch_filter_scan(randt_ctx* ctx, const float* d_raw, int n_scans, int n_az
   A.out_vec = ((uintptr_t)d_out_pts & 15) == 0;
   A.rows = (RowRec*)d_scratch;  // [n_scans * n_az] records, then the stage (api.hip sizes the workspace: FILT_WS_PER_ROW)
   A.stage = (float4*)((char*)d_scratch + (((size_t)n_scans * n_az * sizeof(RowRec) + 255) & ~(size_t)255));
-  // one workgroup per azimuth row; the dispatcher back-fills the chip as workgroups retire
   if ((long long)n_scans * n_az > 0x7fffffffll) return randt_set_error(ctx, RANDT_ERR_UNSUPPORTED, "filter: more than 2^31 azimuth rows in one launch", hipSuccess);
+  return RANDT_OK;
+}
+}  // namespace
+
+int launch_filter_scan(randt_ctx* ctx, const float* d_raw, int n_scans, int n_az, int n_bins, int stride, int ioff,
+                       const randt_filter_params* fp, float* d_out_pts, int pitch_out, int32_t* d_out_counts, float* d_polar,
+                       float* d_peaks, int32_t* d_peak_counts, int32_t* d_status, void* d_scratch) {
+  randt_note_enqueue(ctx);  // (RANDT_SOLVE_AUTO of the process's other contexts: this one has work in flight)
+  FilterArgs A;
+  const int rc = filter_args(ctx, A, n_scans, n_az, n_bins, fp, d_out_pts, pitch_out, d_out_counts, d_polar, d_peaks, d_peak_counts, d_status, d_scratch);
+  if (rc) return rc;
+  A.raw = d_raw;
+  A.stride = stride;
+  A.ioff = ioff;
+  // one workgroup per azimuth row; the dispatcher back-fills the chip as workgroups retire
   const int row_wgs = n_scans * n_az;
   if (stride == 4 && ioff == 3) {
     hipLaunchKernelGGL((k_filter_rows<true, true>), dim3(row_wgs), dim3(FILT_BLOCK), 0, ctx->stream, A);
-    hipLaunchKernelGGL(k_filter_emit<true>, dim3(n_scans), dim3(FILT_EBLOCK), 0, ctx->stream, A);
+    hipLaunchKernelGGL(k_filter_emit<SRC_PACKED>, dim3(n_scans), dim3(FILT_EBLOCK), 0, ctx->stream, A);
   } else if (stride == 4) {
     hipLaunchKernelGGL((k_filter_rows<true, false>), dim3(row_wgs), dim3(FILT_BLOCK), 0, ctx->stream, A);
-    hipLaunchKernelGGL(k_filter_emit<true>, dim3(n_scans), dim3(FILT_EBLOCK), 0, ctx->stream, A);
+    hipLaunchKernelGGL(k_filter_emit<SRC_PACKED>, dim3(n_scans), dim3(FILT_EBLOCK), 0, ctx->stream, A);
   } else {
     hipLaunchKernelGGL((k_filter_rows<false, false>), dim3(row_wgs), dim3(FILT_BLOCK), 0, ctx->stream, A);
-    hipLaunchKernelGGL(k_filter_emit<false>, dim3(n_scans), dim3(FILT_EBLOCK), 0, ctx->stream, A);
+    hipLaunchKernelGGL(k_filter_emit<SRC_STRIDED>, dim3(n_scans), dim3(FILT_EBLOCK), 0, ctx->stream, A);
   }
+  RANDT_HIP_CHECK(ctx, hipGetLastError());
+  return RANDT_OK;
+}
+
+// The same two steps for raster scans (randt_filter_raster_batch_dev, which has validated descriptor and alignment): one
+// wavefront per azimuth row, then the emission over the same row records.
+int launch_filter_raster(randt_ctx* ctx, const void* d_raster, const randt_polar_raster* desc, const float* d_cossin, const float* d_ranges,
+                         int n_scans, const randt_filter_params* fp, float* d_out_pts, int pitch_out, int32_t* d_out_counts, float* d_polar,
+                         float* d_peaks, int32_t* d_peak_counts, int32_t* d_status, void* d_scratch) {
+  randt_note_enqueue(ctx);
+  FilterArgs A;
+  const int rc = filter_args(ctx, A, n_scans, desc->n_azimuths, desc->n_bins, fp, d_out_pts, pitch_out, d_out_counts, d_polar, d_peaks, d_peak_counts,
+                             d_status, d_scratch);
+  if (rc) return rc;
+  A.stride = 4;  // (the expansion's; no kernel of this path reads them)
+  A.ioff = 3;
+  A.raster = static_cast<const unsigned char*>(d_raster);
+  A.cossin = d_cossin;
+  A.ranges = d_ranges;
+  A.row_pitch = desc->row_pitch_bytes;
+  A.scan_pitch = desc->scan_pitch_bytes;
+  A.iscale = desc->intensity_scale;
+  A.elem = desc->elem_type;
+  A.rng_vec = ((uintptr_t)d_ranges & 15) == 0;
+  const dim3 grid(n_scans * desc->n_azimuths), block(FILT_RBLOCK);
+  if (A.elem == RANDT_RASTER_U8) hipLaunchKernelGGL(k_filter_raster_rows<RANDT_RASTER_U8>, grid, block, 0, ctx->stream, A);
+  else if (A.elem == RANDT_RASTER_U16) hipLaunchKernelGGL(k_filter_raster_rows<RANDT_RASTER_U16>, grid, block, 0, ctx->stream, A);
+  else hipLaunchKernelGGL(k_filter_raster_rows<RANDT_RASTER_F32>, grid, block, 0, ctx->stream, A);
+  hipLaunchKernelGGL(k_filter_emit<SRC_RASTER>, dim3(n_scans), dim3(FILT_EBLOCK), 0, ctx->stream, A);
   RANDT_HIP_CHECK(ctx, hipGetLastError());
   return RANDT_OK;
 }

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (CELL_DTYPE, RESULT_DTYPE, STATE_DTYPE, BnbParams, ClusterParams, FilterParams, MapParams, MatcherParams, PgParams, PgResult,
+from ._capi import (CELL_DTYPE, RESULT_DTYPE, STATE_DTYPE, BnbParams, ClusterParams, FilterParams, MapParams, MatcherParams, PgParams, PgResult, PolarRaster,
                     ScParams, WindowParams)
 
 
@@ -537,6 +537,95 @@ def filter_build(ctx, raw, fp, clu, maps, map_idx=0, max_points=6144, intensity_
     st = C.c_int(0)
     ctx._check(ctx._lib.randt_filter_build(ctx._h, _dptr(raw), n_az, n_bins, stride, ioff, C.byref(fp), C.byref(clu), int(max_points), maps._h, int(map_idx),
                                            C.byref(st) if wait else None), "randt_filter_build")
+    return st.value if wait else None
+
+
+# ---- the same filter on azimuth x range intensity rasters (randt_polar_raster)
+_RASTER_TYPES = {np.dtype(np.uint8): _capi.RASTER_U8, np.dtype(np.uint16): _capi.RASTER_U16, np.dtype(np.float32): _capi.RASTER_F32}
+
+
+def polar_tables(azimuths_rad, ranges):
+    """The two tables of a raster scan: cossin (n_az, 2) float32 = (cos, sin) of every azimuth, taken in double and rounded
+    once, and ranges (n_bins,) float32."""
+    az = np.asarray(azimuths_rad, dtype=np.float64).reshape(-1)
+    cossin = np.stack([np.cos(az), np.sin(az)], axis=-1).astype(np.float32)
+    return cossin, np.ascontiguousarray(np.asarray(ranges, dtype=np.float64).reshape(-1).astype(np.float32))
+
+
+def expand_polar_raster(raster, cossin, ranges, scale=1.0):
+    """The EXPANSION of raster scans (include/randt.h): the packed x y z I cloud a converter would build -- x = ranges[b] * c_a,
+    y = ranges[b] * s_a, z = 0, I = float32(v) * scale, one float32 multiply each.  raster: (..., n_az, n_bins) uint8 / uint16 /
+    float32, cossin: (..., n_az, 2) (or one table for all scans), ranges: (n_bins,).  Returns (..., n_az, n_bins, 4) float32:
+    the raster entries return what the point-cloud entries return on it, bit for bit."""
+    raster = np.asarray(raster)
+    if raster.dtype not in _RASTER_TYPES:
+        raise TypeError("raster must be uint8, uint16 or float32, not %s" % raster.dtype)
+    cs = np.asarray(cossin, dtype=np.float32)
+    rg = np.asarray(ranges, dtype=np.float32).reshape(-1)
+    out = np.zeros(raster.shape + (4,), dtype=np.float32)
+    out[..., 0] = rg * cs[..., 0:1]
+    out[..., 1] = rg * cs[..., 1:2]
+    out[..., 3] = raster.astype(np.float32) * np.float32(scale)
+    return out
+
+
+def polar_raster_desc(elem_type, n_az, n_bins, row_pitch_bytes, scan_pitch_bytes=None, scale=1.0):
+    d = PolarRaster()
+    d.elem_type, d.n_azimuths, d.n_bins = int(elem_type), int(n_az), int(n_bins)
+    d.row_pitch_bytes = int(row_pitch_bytes)
+    d.scan_pitch_bytes = int(n_az) * int(row_pitch_bytes) if scan_pitch_bytes is None else int(scan_pitch_bytes)
+    d.intensity_scale = float(scale)
+    return d
+
+
+def _host_raster(raster):
+    """A 2-D numpy raster with contiguous rows and its descriptor fields.  The array may be a view into a wider buffer, e.g.
+    ``image[:, 11:]`` of an Oxford radar PNG: any row pitch and start address are handed over as they are."""
+    if raster.dtype not in _RASTER_TYPES:
+        raise TypeError("raster must be uint8, uint16 or float32, not %s" % raster.dtype)
+    if raster.ndim != 2:
+        raise ValueError("one raster scan is a 2-D array (n_azimuths, n_bins), not %d-D" % raster.ndim)
+    if (raster.shape[1] > 1 and raster.strides[1] != raster.itemsize) or raster.strides[0] < raster.shape[1] * raster.itemsize:
+        raster = np.ascontiguousarray(raster)
+    return raster, _RASTER_TYPES[raster.dtype], int(raster.shape[0]), int(raster.shape[1]), int(raster.strides[0])
+
+
+def filter_raster_batch(ctx, raster, desc, cossin, ranges, n_scans, fp, out_points, out_counts, status, out_polar=None, peaks=None,
+                        peak_counts=None):
+    """randt_filter_raster_batch_dev.  raster: device memory laid out as `desc` (polar_raster_desc) says, cossin:
+    (n_scans, n_az, 2) and ranges: (n_bins,) float32 device tensors; outputs as filter_scan_batch."""
+    ctx._check(ctx._lib.randt_filter_raster_batch_dev(ctx._h, _dptr(raster), C.byref(desc), _dptr(cossin), _dptr(ranges), int(n_scans), C.byref(fp),
+                                                      _dptr(out_points), int(out_points.shape[1]), _dptr(out_counts), _dptr(out_polar),
+                                                      _dptr(peaks), _dptr(peak_counts), _dptr(status)), "randt_filter_raster_batch_dev")
+
+
+def filter_raster_host(ctx, raster, cossin, ranges, fp, scale=1.0, capacity=8192, want_polar=True, want_peaks=True):
+    """randt_filter_raster: ONE raster scan in host memory (2-D numpy, uint8 / uint16 / float32, possibly a view with a row
+    pitch of its own), results on the host as filter_scan_host returns them."""
+    raster, et, n_az, n_bins, pitch = _host_raster(np.asarray(raster))
+    cossin = np.ascontiguousarray(cossin, dtype=np.float32).reshape(n_az, 2)
+    ranges = np.ascontiguousarray(ranges, dtype=np.float32).reshape(n_bins)
+    desc = polar_raster_desc(et, n_az, n_bins, pitch, scale=scale)
+    pts = np.zeros((capacity, 4), dtype=np.float32)
+    pol = np.zeros((capacity, 2), dtype=np.float32) if want_polar else None
+    pk = np.zeros((n_az, 3), dtype=np.float32) if want_peaks else None
+    n, npk, st = C.c_int(0), C.c_int(0), C.c_int(0)
+    ctx._check(ctx._lib.randt_filter_raster(ctx._h, _dptr(raster), C.byref(desc), _dptr(cossin), _dptr(ranges), C.byref(fp), _dptr(pts), capacity,
+                                            C.byref(n), _dptr(pol), _dptr(pk), C.byref(npk), C.byref(st)), "randt_filter_raster")
+    m = min(n.value, capacity)
+    return pts[:m], (pol[:m] if want_polar else None), (pk[:npk.value] if want_peaks else None), n.value, st.value
+
+
+def filter_raster_build(ctx, raster, cossin, ranges, fp, clu, maps, map_idx=0, scale=1.0, max_points=6144, wait=True):
+    """randt_filter_raster_build: raster scan in host memory -> filterScan -> clustering + NDT into maps[map_idx], on the device.
+    Returns the filter's status (wait=False: asynchronous after the upload, returns None)."""
+    raster, et, n_az, n_bins, pitch = _host_raster(np.asarray(raster))
+    cossin = np.ascontiguousarray(cossin, dtype=np.float32).reshape(n_az, 2)
+    ranges = np.ascontiguousarray(ranges, dtype=np.float32).reshape(n_bins)
+    desc = polar_raster_desc(et, n_az, n_bins, pitch, scale=scale)
+    st = C.c_int(0)
+    ctx._check(ctx._lib.randt_filter_raster_build(ctx._h, _dptr(raster), C.byref(desc), _dptr(cossin), _dptr(ranges), C.byref(fp), C.byref(clu),
+                                                  int(max_points), maps._h, int(map_idx), C.byref(st) if wait else None), "randt_filter_raster_build")
     return st.value if wait else None
 
 

@@ -62,16 +62,41 @@ class HipBackend:
         host.ndt_build_batch(self.ctx, pts.reshape(1, pts.shape[-2], pts.shape[-1]), self.clu, self.scans, first_map=idx)
         return idx
 
-    def build_scan_from_polar(self, raw, filter_params, pitch_out=6144):
-        """BASELINE config 5 front end: RadarPreprocessor::filterScan on a raw polar scan
-        (n_azimuths x n_bins x stride, device tensor) followed by the NDT build of the kept points."""
+    def _filter_outputs(self, pitch_out):
+        """the filter's device outputs (points, count, status), allocated once per pitch"""
         torch = self.torch
         if getattr(self, "_f_out", None) is None or self._f_out.shape[1] != pitch_out:
             self._f_out = torch.zeros((1, pitch_out, 4), dtype=torch.float32, device=self.dev)
             self._f_cnt = torch.zeros(1, dtype=torch.int32, device=self.dev)
             self._f_status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+
+    def build_scan_from_polar(self, raw, filter_params, pitch_out=6144):
+        """BASELINE config 5 front end: RadarPreprocessor::filterScan on a raw polar scan
+        (n_azimuths x n_bins x stride, device tensor) followed by the NDT build of the kept points."""
+        torch = self.torch
+        self._filter_outputs(pitch_out)
         raw = raw if hasattr(raw, "data_ptr") else torch.from_numpy(np.ascontiguousarray(raw, dtype=np.float32)).to(self.dev)
         host.filter_scan_batch(self.ctx, raw.reshape(1, *raw.shape[-3:]), filter_params, self._f_out, self._f_cnt, self._f_status)
+        idx = self._take(self.free_scans, "scan", "scan_slots")
+        host.ndt_build_batch(self.ctx, self._f_out, self.clu, self.scans, first_map=idx, n_points=self._f_cnt)
+        return idx
+
+    def build_scan_from_polar_raster(self, raster, cossin, ranges, filter_params, scale=1.0, pitch_out=6144):
+        """The same front end for a scan delivered as an azimuth x range intensity raster (n_azimuths x n_bins, uint8 / uint16 /
+        float32 numpy) with its tables (host.polar_tables): the raster itself is uploaded, 1/16 of the point cloud's bytes for
+        uint8, and randt_filter_raster_batch_dev returns what filterScan returns on host.expand_polar_raster(...)."""
+        torch = self.torch
+        self._filter_outputs(pitch_out)
+        raster, et, n_az, n_bins, _ = host._host_raster(np.asarray(raster))
+        row = n_bins * raster.itemsize
+        pitch = (row + 15) & ~15                                                          # the device rows are 16-byte aligned
+        buf = np.zeros((n_az, pitch), dtype=np.uint8)
+        buf[:, :row] = np.ascontiguousarray(raster).view(np.uint8).reshape(n_az, row)
+        d_ras = torch.from_numpy(buf).to(self.dev)
+        d_cs = torch.from_numpy(np.ascontiguousarray(cossin, dtype=np.float32).reshape(1, n_az, 2)).to(self.dev)
+        d_rg = torch.from_numpy(np.ascontiguousarray(ranges, dtype=np.float32).reshape(n_bins)).to(self.dev)
+        desc = host.polar_raster_desc(et, n_az, n_bins, pitch, scale=scale)
+        host.filter_raster_batch(self.ctx, d_ras, desc, d_cs, d_rg, 1, filter_params, self._f_out, self._f_cnt, self._f_status)
         idx = self._take(self.free_scans, "scan", "scan_slots")
         host.ndt_build_batch(self.ctx, self._f_out, self.clu, self.scans, first_map=idx, n_points=self._f_cnt)
         return idx
@@ -365,17 +390,25 @@ class Odometry:
             b.merge(self.current_submap, scan, self.current_transform)                    # :281,293
             self.current_submap_is_empty = False
 
-    def process_scan(self, points, stamp, polar_filter=None, imu_yaw_increment=0.0):
+    def process_scan(self, points, stamp, polar_filter=None, imu_yaw_increment=0.0, polar_raster=None):
         """NDTSlam::radarCb (ndt_slam.cpp:211-223): process, roll the submap over when complete.
         polar_filter: FilterParams -> `points` is a raw polar scan and goes through filterScan first.
+        polar_raster: (cossin, ranges) or (cossin, ranges, intensity_scale) -> `points` is an azimuth x range intensity raster
+        (uint8 / uint16 / float32) with these tables; needs polar_filter.
         imu_yaw_increment: the heading change since the last scan from the IMU (local_fuser.cpp:107-121), used when
         window_params.use_imu is set."""
         if self._refs is None:
             self._refs = {}
         self._yaw = float(imu_yaw_increment)
         self._cur_points = points
+        if polar_raster is not None and polar_filter is None:
+            raise ValueError("polar_raster needs polar_filter (the FilterParams of filterScan)")
         if polar_filter is not None:
-            scan = self.b.build_scan_from_polar(points, polar_filter)                     # :102 filterScan + clustering
+            if polar_raster is not None:
+                scan = self.b.build_scan_from_polar_raster(points, polar_raster[0], polar_raster[1], polar_filter,
+                                                           scale=polar_raster[2] if len(polar_raster) > 2 else 1.0)
+            else:
+                scan = self.b.build_scan_from_polar(points, polar_filter)                 # :102 filterScan + clustering
             if self.keep_filtered_points:                                                 # the SLAM layer feeds them to Scan Context
                 self._cur_points = self.b.filtered_points()
         else:
