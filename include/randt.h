@@ -460,7 +460,9 @@ int randt_sc_make_batch_dev(randt_ctx* ctx, const float* d_points, int n_scans, 
  * (descriptors / ring keys as produced above, odometry positions [n_db][2], traversed distances [n_db]).  Query q is node
  * d_query_ids[q] (NULL: q) and searches nodes [0, node - num_exclude_recent].  d_loop_id[q] = matched node or -1,
  * d_yaw[q] = relative yaw [rad], d_min_dist (nullable) = best combined distance.  The reference's KD-tree (rebuilt only
- * every tree_making_period queries) is replaced by an exact search over the current database. */
+ * every tree_making_period queries) is replaced by an exact search over the current database.  A node whose float
+ * key distance to the query is NaN (a NaN intensity in either scan) is never a candidate; a NaN node as a query finds nothing
+ * (-1, distance 10000000).  An infinite key distance is a distance like any other: it ranks last. */
 int randt_sc_detect_batch_dev(randt_ctx* ctx, const randt_sc_params* p, const double* d_desc, const double* d_ring_keys,
                               const double* d_pos, const double* d_dist, int n_db, const int32_t* d_query_ids, int n_queries,
                               int32_t* d_loop_id, float* d_yaw, double* d_min_dist);

@@ -2483,6 +2483,10 @@ int orc_sc_detect(const orc_sc_params* p, const double* desc, const double* ring
     int best = -1;
     for (int i = 0; i < n_search; ++i)
       if (d2[i] >= 0.0f && (best < 0 || d2[i] < d2[best])) best = i;
+    /* SPEC DECISION: an entry whose float key distance is not >= 0 (NaN: a NaN ring key on either side, or inf - inf) is never a
+     * candidate; when no candidate is left the remaining ranks are absent (the reference hands such keys to nanoflann,
+     * whose result set is then unspecified) */
+    if (best < 0) break;
     d2[best] = -1.0f; /* taken */
     int sh;
     const double d = orc_sc_distance(p, desc + (size_t)node_id * R * S, desc + (size_t)best * R * S, pos + 2 * (size_t)node_id,

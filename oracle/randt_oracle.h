@@ -268,7 +268,9 @@ int orc_filter_scan(const float* raw, int n, int stride, int ioff, const orc_fil
  * SPEC DECISIONS: xy2theta calls the unqualified atan on a float -> the correctly rounded float arctangent; Eigen's .mean() /
  * .norm() / .dot() reduction order depends on the reference's build flags -> plain left-to-right sums here
  * (GPU parity is by tolerance); the nanoflann KD-tree search is restated as an exact brute-force kNN in float
- * (ties: lower index first); the tree is rebuilt on every query (TREE_MAKING_PERIOD = 1 semantics). */
+ * (ties: lower index first); the tree is rebuilt on every query (TREE_MAKING_PERIOD = 1 semantics); an entry whose float
+ * key distance to the query is not >= 0 (a NaN distance; +inf is a distance like any other) is never a candidate, and when no candidate is left the
+ * remaining ranks are absent. */
 typedef struct orc_sc_params {
   int num_ring, num_sector;          /* PC_NUM_RING, PC_NUM_SECTOR */
   double max_radius;                 /* PC_MAX_RADIUS */

@@ -233,7 +233,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_sc_knn(ScParams P, const double* _
       if (tid == 0) cand[c] = -1;
       continue;
     }
-    double bv = 1e300;
+    double bv = INFINITY;  // (not a large finite value: a +inf distance IS >= 0 and is taken, lowest index first, by the == clause)
     int bi = 0x7fffffff;
     for (int i = tid; i < n_search; i += SC_BLOCK) {
       const float v = d2[i];
@@ -243,9 +243,11 @@ __global__ __launch_bounds__(SC_BLOCK) void k_sc_knn(ScParams P, const double* _
       }
     }
     block_argmin(bv, bi, sv, si);
+    // an entry whose key distance is not >= 0 (NaN: a NaN ring key on either side, or inf - inf) is never a candidate: when none
+    // is left, this rank and every later one are absent and nothing is retired.  A +inf distance ranks last like any other value
     if (tid == 0) {
-      cand[c] = bi;
-      d2[bi] = -1.0f;
+      cand[c] = bi == 0x7fffffff ? -1 : bi;
+      if (bi != 0x7fffffff) d2[bi] = -1.0f;
     }
     __syncthreads();
   }
