@@ -466,6 +466,20 @@ int randt_sc_make_batch_dev(randt_ctx* ctx, const float* d_points, int n_scans, 
 int randt_sc_detect_batch_dev(randt_ctx* ctx, const randt_sc_params* p, const double* d_desc, const double* d_ring_keys,
                               const double* d_pos, const double* d_dist, int n_db, const int32_t* d_query_ids, int n_queries,
                               int32_t* d_loop_id, float* d_yaw, double* d_min_dist);
+/* Place recognition for scans that are NOT nodes of the database (relocalisation, localisation in an earlier session's map):
+ * detectLoopClosureID with the query's descriptor, ring key, position and traversed distance taken from arrays of their own,
+ * laid out per query like the database's ([n_queries][num_sector][num_ring], [n_queries][num_ring], [n_queries][2],
+ * [n_queries]).  Query q searches ALL n_db nodes; num_exclude_recent is not read.  With d_q_pos and d_q_dist both given, a
+ * candidate's total distance is the reference's formula with the query in the node's place; with either NULL the odometry
+ * term is left out (the total is the descriptor distance alone) and d_pos / d_dist may be NULL too.  d_loop_id, d_yaw,
+ * d_min_dist (nullable): as above; n_db == 0 gives -1, 0, 10000000.  Per candidate, [n_queries][num_candidates], each nullable:
+ * d_cand_id = the database index of rank c in (float key distance, index) order, d_cand_dist = its total distance (not
+ * thresholded), d_cand_yaw = the yaw of its own argmin shift; absent ranks hold -1 / 0 / 10000000.  NaN and infinite key
+ * distances, limits and errors as above.  Enqueue-only; the workspace comes from the context's storage pool. */
+int randt_sc_query_batch_dev(randt_ctx* ctx, const randt_sc_params* p, const double* d_desc, const double* d_ring_keys,
+                             const double* d_pos, const double* d_dist, int n_db, const double* d_q_desc, const double* d_q_ring_keys,
+                             const double* d_q_pos, const double* d_q_dist, int n_queries, int32_t* d_loop_id, float* d_yaw,
+                             double* d_min_dist, int32_t* d_cand_id, float* d_cand_yaw, double* d_cand_dist);
 
 /* Device-resident Scan Context database = the state SCManager keeps (polarcontexts_, polarcontext_invkeys_mat_,
  * odom_positions_, distances_; include/local_fuser/Scancontext.h:88-99).  Nodes are appended in keyframe order. */
@@ -481,6 +495,16 @@ int randt_sc_db_append(randt_sc_db* db, const float* h_points, int n_points, int
 /* SCManager::detectLoopClosureID (Scancontext.cpp:261-341) for one node of the database: *loop_id = match or -1,
  * *yaw_diff_rad as in the reference's return value, *min_dist (nullable). */
 int randt_sc_db_detect(randt_sc_db* db, int node_id, int* loop_id, float* yaw_diff_rad, double* min_dist);
+/* randt_sc_query_batch_dev for one HOST scan against the handle's database, which stays as it is (same size, same contents):
+ * the scan's descriptor and keys are made in workspace.  odom_position [2] and traversed_distance (both nullable; the prior is
+ * used only when both are given).  h_cand_id / h_cand_yaw / h_cand_dist: [num_candidates] each, nullable. */
+int randt_sc_db_query(randt_sc_db* db, const float* h_points, int n_points, int stride_floats, int intensity_index,
+                      const double* odom_position, const double* traversed_distance, int* loop_id, float* yaw_diff_rad, double* min_dist,
+                      int32_t* h_cand_id, float* h_cand_yaw, double* h_cand_dist);
+/* Stores a node from exactly what randt_sc_db_download returns (plus its odometry): a prior map's database is restored
+ * without its raw scans, and answers randt_sc_db_detect / randt_sc_db_query bit for bit like the original. */
+int randt_sc_db_append_node(randt_sc_db* db, const double* h_desc, const double* h_ring_key, const double* h_sector_key,
+                            const double odom_position[2], double traversed_distance, int* node_id);
 /* host copies of one node (debug / tests): h_desc [num_sector][num_ring], h_ring_key [num_ring], h_sector_key [num_sector]
  * (each nullable) */
 int randt_sc_db_download(const randt_sc_db* db, int node_id, double* h_desc, double* h_ring_key, double* h_sector_key);

@@ -1256,6 +1256,7 @@ class SCManager {
     p.odom_eps = params.odom_eps;
     p.odom_weight = params.odom_weight;
     p.intensity_factor = params.intensity_factor;
+    n_candidates_ = p.num_candidates > 0 ? p.num_candidates : 1;
     randt_sc_db_destroy(db_);
     db_ = nullptr;
     const int rc = randt_sc_db_create(ctx_->get(), &p, 256, &db_);
@@ -1279,11 +1280,55 @@ class SCManager {
     return {loop_id, yaw};
   }
 
+  // NOT in the reference: place recognition for a scan that is no node of the database (relocalisation after a restart or
+  // a tracking loss, a scan of another session).  The scan is compared with ALL nodes; the database stays as it is.
+  // Same return value as detectLoopClosureID.  With odom_position and traversed_distance the odometry term of
+  // distanceBtnScanContext is formed with the scan in the node's place; without them it is left out.
+  // candidates (nullable): every candidate in rank order, absent ranks as -1 / 0 / 10000000 (randt_sc_query_batch_dev).
+  struct Candidates {
+    std::vector<int32_t> id;
+    std::vector<float> yaw;
+    std::vector<double> dist;
+  };
+  std::pair<int, float> queryLoopClosure(const float* points, int n, int stride, int intensity_index, Candidates* candidates = nullptr) const {
+    return query(points, n, stride, intensity_index, nullptr, nullptr, candidates);
+  }
+  std::pair<int, float> queryLoopClosure(const float* points, int n, int stride, int intensity_index, const std::array<double, 2>& odom_position,
+                                         const double& traversed_distance, Candidates* candidates = nullptr) const {
+    return query(points, n, stride, intensity_index, odom_position.data(), &traversed_distance, candidates);
+  }
+
+  // NOT in the reference: a node from its stored descriptor and keys (what randt_sc_db_download returns: desc
+  // [num_sector][num_ring], ring_key [num_ring], sector_key [num_sector]) instead of its scan -- a prior map's database
+  // restored without the raw scans.
+  void appendNode(const double* desc, const double* ring_key, const double* sector_key, const std::array<double, 2>& odom_position,
+                  const double& traversed_distance) {
+    const int rc = randt_sc_db_append_node(db_, desc, ring_key, sector_key, odom_position.data(), traversed_distance, nullptr);
+    facade_check(rc, "randt_sc_db_append_node", ctx_ ? ctx_->get() : nullptr);
+  }
+
   int size() const { return randt_sc_db_size(db_); }
 
  private:
+  std::pair<int, float> query(const float* points, int n, int stride, int intensity_index, const double* odom_position,
+                              const double* traversed_distance, Candidates* candidates) const {
+    int loop_id = -1;
+    float yaw = 0.f;
+    if (candidates) {
+      candidates->id.assign(n_candidates_, -1);
+      candidates->yaw.assign(n_candidates_, 0.f);
+      candidates->dist.assign(n_candidates_, 10000000.0);
+    }
+    const int rc = randt_sc_db_query(db_, points, n, stride, intensity_index, odom_position, traversed_distance, &loop_id, &yaw, nullptr,
+                                     candidates ? candidates->id.data() : nullptr, candidates ? candidates->yaw.data() : nullptr,
+                                     candidates ? candidates->dist.data() : nullptr);
+    if (!facade_check(rc, "randt_sc_db_query", ctx_ ? ctx_->get() : nullptr)) return {-1, 0.f};  // "no place found"
+    return {loop_id, yaw};
+  }
+
   std::shared_ptr<Context> ctx_;
   randt_sc_db* db_ = nullptr;
+  int n_candidates_ = 1;
 };
 
 // Pose / Constraint (include/ndt_slam/trajectory_representation.h:25-52): graph node and edge.  Matrices row-major.

@@ -178,6 +178,9 @@ SYMBOLS = {
     "randt_filter_raster_build": (_I, [_V, _V, _P(PolarRaster), _V, _V, _P(FilterParams), _P(ClusterParams), _I, _V, _I, _P(_I)]),
     "randt_sc_make_batch_dev": (_I, [_V, _V, _I, _I, _V, _I, _I, _P(ScParams), _V, _V, _V]),
     "randt_sc_detect_batch_dev": (_I, [_V, _P(ScParams), _V, _V, _V, _V, _I, _V, _I, _V, _V, _V]),
+    "randt_sc_query_batch_dev": (_I, [_V, _P(ScParams), _V, _V, _V, _V, _I, _V, _V, _V, _V, _I, _V, _V, _V, _V, _V, _V]),
+    "randt_sc_db_query": (_I, [_V, _V, _I, _I, _I, _V, _P(C.c_double), _P(_I), _P(C.c_float), _P(C.c_double), _V, _V, _V]),
+    "randt_sc_db_append_node": (_I, [_V, _V, _V, _V, _V, C.c_double, _P(_I)]),
     "randt_sc_db_create": (_I, [_V, _P(ScParams), _I, _P(_V)]),
     "randt_sc_db_destroy": (None, [_V]),
     "randt_sc_db_size": (_I, [_V]),

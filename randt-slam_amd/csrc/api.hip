@@ -1489,6 +1489,21 @@ int randt_sc_detect_batch_dev(randt_ctx* ctx, const randt_sc_params* p, const do
                           d_min_dist);
 }
 
+int randt_sc_query_batch_dev(randt_ctx* ctx, const randt_sc_params* p, const double* d_desc, const double* d_ring_keys,
+                             const double* d_pos, const double* d_dist, int n_db, const double* d_q_desc, const double* d_q_ring_keys,
+                             const double* d_q_pos, const double* d_q_dist, int n_queries, int32_t* d_loop_id, float* d_yaw,
+                             double* d_min_dist, int32_t* d_cand_id, float* d_cand_yaw, double* d_cand_dist) {
+  DeviceGuard dev_guard__(ctx);
+  if (!ctx || !p || n_db < 0 || n_queries < 0) return RANDT_ERR_INVALID;
+  if (n_queries == 0) return RANDT_OK;
+  if (!d_q_desc || !d_q_ring_keys || !d_loop_id || !d_yaw || (n_db > 0 && (!d_desc || !d_ring_keys))) return RANDT_ERR_INVALID;
+  if (d_q_pos && d_q_dist && n_db > 0 && (!d_pos || !d_dist)) return RANDT_ERR_INVALID;  // a prior needs the nodes' odometry
+  int rc = randt_scratch_reserve(ctx, ctx->ws, sc_query_ws_bytes(n_queries, n_db, p->num_candidates));
+  if (rc) return rc;
+  return launch_sc_query(ctx, p, d_desc, d_ring_keys, d_pos, d_dist, n_db, d_q_desc, d_q_ring_keys, d_q_pos, d_q_dist, n_queries, ctx->ws.p,
+                         d_loop_id, d_yaw, d_min_dist, d_cand_id, d_cand_yaw, d_cand_dist);
+}
+
 // ---------------------------------------------------------------- Scan Context database -----------------
 struct randt_sc_db {
   randt_ctx* ctx = nullptr;
@@ -1606,6 +1621,91 @@ int randt_sc_db_detect(randt_sc_db* db, int node_id, int* loop_id, float* yaw_di
   RANDT_HIP_CHECK(ctx, randt_sync(ctx));
   *loop_id = id;
   if (min_dist) *min_dist = md;
+  return RANDT_OK;
+}
+
+int randt_sc_db_query(randt_sc_db* db, const float* h_points, int n_points, int stride_floats, int intensity_index,
+                      const double* odom_position, const double* traversed_distance, int* loop_id, float* yaw_diff_rad, double* min_dist,
+                      int32_t* h_cand_id, float* h_cand_yaw, double* h_cand_dist) {
+  DeviceGuard dev_guard__(db ? db->ctx : nullptr);
+  if (!db || !loop_id || !yaw_diff_rad || n_points < 0 || (n_points > 0 && !h_points) || stride_floats < 3 || intensity_index < 0 ||
+      intensity_index >= stride_floats)
+    return RANDT_ERR_INVALID;
+  randt_ctx* ctx = db->ctx;
+  const randt_sc_params& p = db->p;
+  const int pitch = n_points > 0 ? n_points : 1;
+  const size_t k = p.num_candidates > 0 ? p.num_candidates : 1, ws_bytes = sc_query_ws_bytes(1, db->n, p.num_candidates);
+  // the scan, its descriptor and keys, the prior, the outputs, and launch_sc_query's workspace: the database itself is only read
+  struct Layout {
+    float* pts;
+    int32_t* n;
+    double *desc, *ring, *sector, *prior, *md, *cand_dist;
+    int32_t *id, *cand_id;
+    float *yaw, *cand_yaw;
+    char* ws;
+  };
+  auto layout = [&](Carve& c) {
+    Layout L;
+    L.pts = c.take<float>((size_t)pitch * stride_floats);
+    L.n = c.take<int32_t>(1, 16);
+    L.desc = c.take<double>((size_t)p.num_ring * p.num_sector);
+    L.ring = c.take<double>(p.num_ring, 16);
+    L.sector = c.take<double>(p.num_sector, 16);
+    L.prior = c.take<double>(3, 16);
+    L.md = c.take<double>(1, 16);
+    L.cand_dist = c.take<double>(k, 16);
+    L.id = c.take<int32_t>(1, 16);
+    L.cand_id = c.take<int32_t>(k, 16);
+    L.yaw = c.take<float>(1, 16);
+    L.cand_yaw = c.take<float>(k, 16);
+    L.ws = c.take<char>(ws_bytes);
+    return L;
+  };
+  int rc = randt_scratch_reserve(ctx, ctx->ws, carved_size(layout));
+  if (rc) return rc;
+  Carve c(ctx->ws.p);
+  const Layout L = layout(c);
+  if (n_points > 0) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.pts, h_points, sizeof(float) * (size_t)pitch * stride_floats, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.n, &n_points, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  const bool prior = odom_position && traversed_distance;
+  const double pd[3] = {prior ? odom_position[0] : 0.0, prior ? odom_position[1] : 0.0, prior ? *traversed_distance : 0.0};
+  if (prior) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(L.prior, pd, sizeof(pd), hipMemcpyHostToDevice, ctx->stream));
+  rc = launch_sc_make(ctx, L.pts, 1, pitch, L.n, stride_floats, intensity_index, &p, L.desc, L.ring, L.sector);
+  if (rc) return drained(ctx, rc);
+  rc = launch_sc_query(ctx, &p, db->desc, db->ring, db->pos, db->dist, db->n, L.desc, L.ring, prior ? L.prior : nullptr, prior ? L.prior + 2 : nullptr, 1,
+                       L.ws, L.id, L.yaw, L.md, L.cand_id, L.cand_yaw, L.cand_dist);
+  if (rc) return drained(ctx, rc);
+  int32_t id = -1;
+  double md = 0;
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(&id, L.id, sizeof(id), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(yaw_diff_rad, L.yaw, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(&md, L.md, sizeof(md), hipMemcpyDeviceToHost, ctx->stream));
+  if (h_cand_id) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_cand_id, L.cand_id, sizeof(int32_t) * k, hipMemcpyDeviceToHost, ctx->stream));
+  if (h_cand_yaw) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_cand_yaw, L.cand_yaw, sizeof(float) * k, hipMemcpyDeviceToHost, ctx->stream));
+  if (h_cand_dist) RANDT_HIP_CHECK(ctx, hipMemcpyAsync(h_cand_dist, L.cand_dist, sizeof(double) * k, hipMemcpyDeviceToHost, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));
+  *loop_id = id;
+  if (min_dist) *min_dist = md;
+  return RANDT_OK;
+}
+
+int randt_sc_db_append_node(randt_sc_db* db, const double* h_desc, const double* h_ring_key, const double* h_sector_key,
+                            const double odom_position[2], double traversed_distance, int* node_id) {
+  DeviceGuard dev_guard__(db ? db->ctx : nullptr);
+  if (!db || !h_desc || !h_ring_key || !h_sector_key || !odom_position) return RANDT_ERR_INVALID;
+  randt_ctx* ctx = db->ctx;
+  int rc = sc_db_reserve(db, db->n + 1);
+  if (rc) return rc;
+  const size_t R = db->p.num_ring, S = db->p.num_sector, n = db->n;
+  const double pd[3] = {odom_position[0], odom_position[1], traversed_distance};
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(db->desc + R * S * n, h_desc, sizeof(double) * R * S, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(db->ring + R * n, h_ring_key, sizeof(double) * R, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(db->sector + S * n, h_sector_key, sizeof(double) * S, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(db->pos + 2 * n, pd, sizeof(double) * 2, hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, hipMemcpyAsync(db->dist + n, pd + 2, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  RANDT_HIP_CHECK(ctx, randt_sync(ctx));  // the host buffers may go away
+  if (node_id) *node_id = db->n;
+  db->n += 1;
   return RANDT_OK;
 }
 

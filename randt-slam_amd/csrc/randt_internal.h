@@ -287,6 +287,12 @@ size_t sc_detect_ws_bytes(int n_queries, int n_db, int n_cand);  // workspace la
 int launch_sc_detect(randt_ctx* ctx, const randt_sc_params* p, const double* d_desc, const double* d_ring_keys, const double* d_pos,
                      const double* d_dist, int n_db, const int32_t* d_query_ids, int n_queries, float* d_ws, int32_t* d_loop_id,
                      float* d_yaw, double* d_min_dist);
+// scancontext_query.hip: a query from outside the database (all n_db nodes searched; d_q_pos / d_q_dist NULL: no odometry term)
+size_t sc_query_ws_bytes(int n_queries, int n_db, int n_cand);  // workspace launch_sc_query needs behind d_ws
+int launch_sc_query(randt_ctx* ctx, const randt_sc_params* p, const double* d_desc, const double* d_ring_keys, const double* d_pos,
+                    const double* d_dist, int n_db, const double* d_q_desc, const double* d_q_ring_keys, const double* d_q_pos,
+                    const double* d_q_dist, int n_queries, void* d_ws, int32_t* d_loop_id, float* d_yaw, double* d_min_dist,
+                    int32_t* d_cand_id, float* d_cand_yaw, double* d_cand_dist);
 
 int launch_points_transform(randt_ctx* ctx, float* d_pts, int n, int stride, const double* d_pose4);
 int launch_cells_op(randt_ctx* ctx, int op, randt_cell* d_a, const randt_cell* d_b, int n, const double* d_pose4, double* d_out);

@@ -25,12 +25,9 @@
 #define SC_MAX_CAND 32
 #define SC_TERM_CAP 4096  // (shift, column) cosine terms of one candidate kept in LDS (32 KB): (2 radius + 1) x num_sector <= this
 
-namespace {
+#include "scancontext_shared.h"  // ScParams, ScCandidate, block_argmin, the (query, candidate) distance: shared with scancontext_query.hip
 
-struct ScParams {
-  int R, S, exclude_recent, n_cand, radius;
-  double max_radius, dist_thresh, assumed_drift, odom_eps, odom_weight, intensity_factor;
-};
+namespace {
 
 // xy2theta (Scancontext.cpp:24-37); the arctangent is evaluated in double and rounded to float (= the correctly
 // rounded float arctangent, identical on host and device)
@@ -165,40 +162,6 @@ __global__ __launch_bounds__(SC_BLOCK) void k_sc_make(const float* __restrict__ 
   }
 }
 
-// lexicographic (value, index) block arg-min over 256 threads; result broadcast.  scratch: 2 x 4 words.
-__device__ __forceinline__ void block_argmin(double& v, int& idx, double* sv, int* si) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double ov = __shfl_xor(v, off, 64);
-    const int oi = __shfl_xor(idx, off, 64);
-    if (ov < v || (ov == v && oi < idx)) {
-      v = ov;
-      idx = oi;
-    }
-  }
-  __syncthreads();
-  if (lane == 0) {
-    sv[wave] = v;
-    si[wave] = idx;
-  }
-  __syncthreads();
-  v = sv[0];
-  idx = si[0];
-#pragma unroll
-  for (int w = 1; w < SC_BLOCK / 64; ++w)
-    if (sv[w] < v || (sv[w] == v && si[w] < idx)) {
-      v = sv[w];
-      idx = si[w];
-    }
-}
-
-// what a (query, candidate) workgroup leaves for k_sc_pick
-struct ScCandidate {
-  double cd;           // distanceBtnScanContext + the odometry term
-  int32_t shift, idx;  // argmin shift, database index (-1: this query has fewer candidates)
-};
-
 // The candidate search of a query, once (every (query, rank) workgroup used to repeat it on a distance row of its
 // own -- n_queries x n_candidates x n_db floats of workspace): the squared float distances of the ring keys (nanoflann L2,
 // accumulated in float) and the k nearest keys in ascending (distance, index) order.  One workgroup per query; cand_out
@@ -260,15 +223,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_sc_detect(ScParams P, const double
                                                         const double* __restrict__ pos, const double* __restrict__ dist, int n_db,
                                                         const int32_t* __restrict__ query_ids, const int32_t* __restrict__ cand_in,
                                                         ScCandidate* __restrict__ records, int staged) {
-  // staged: the query's and the current candidate's descriptor (S x R doubles each) are copied into LDS with coalesced loads;
-  // every dot product below then reads LDS instead of walking two global columns element by element (a candidate cost 12 us of
-  // L2 round trips that way).  Descriptors too large for it stay in global memory.
-  extern __shared__ __attribute__((aligned(16))) char sc_dyn[];
-  __shared__ double k1[SC_MAX_SECTOR], k2[SC_MAX_SECTOR];
-  __shared__ double n1[SC_MAX_SECTOR], n2[SC_MAX_SECTOR];  // column norms of the query / the candidate (shift-independent)
-  __shared__ double term[SC_TERM_CAP];
-  __shared__ double sv[4];
-  __shared__ int si[4];
+  // staged / spread_shifts: see sc_descriptor_distance (scancontext_shared.h), which holds this kernel's arithmetic
   const int q = blockIdx.x, c_only = blockIdx.y, tid = threadIdx.x;
   const int node = query_ids ? query_ids[q] : q;
   const int R = P.R, S = P.S;
@@ -278,159 +233,17 @@ __global__ __launch_bounds__(SC_BLOCK) void k_sc_detect(ScParams P, const double
     if (tid == 0) rec->idx = -1;
     return;
   }
-  // ---- pairwise distances (distanceBtnScanContext) in candidate order
-  const double* sc1 = desc + (size_t)node * R * S;
-  double* s1 = reinterpret_cast<double*>(sc_dyn);
-  double* s2 = s1 + (size_t)R * S;
-  if (staged) {
-    for (int i = tid; i < R * S; i += SC_BLOCK) s1[i] = sc1[i];
-    __syncthreads();
-    sc1 = s1;
-  }
-  // The column-shift search evaluates, per shift, sum over the columns of dot / (|a| |b|): the norms do not depend on the shift
-  // and the (shift, column) dot products not on each other, so they are formed once / by all 256 threads; only each shift's sum
-  // over the columns stays one thread's left-to-right loop (the reference's order) -- same numbers, ~30x less serial work.
   const int n_shift = 2 * P.radius + 1;
   const bool spread_shifts = n_shift <= S && n_shift * S <= SC_TERM_CAP;
-  if (tid < S) {
-    double a = 0, na = 0;
-#pragma unroll 4
-    for (int r = 0; r < R; ++r) {
-      const double v = sc1[(size_t)tid * R + r];
-      a += v;
-      na += v * v;
-    }
-    k1[tid] = a / R;
-    n1[tid] = sqrt(na);
-  }
-  {
-    const double* sc2 = desc + (size_t)ci * R * S;
-    __syncthreads();
-    if (staged) {
-      for (int i = tid; i < R * S; i += SC_BLOCK) s2[i] = sc2[i];
-      __syncthreads();
-      sc2 = s2;
-    }
-    if (tid < S) {
-      double b = 0, nb = 0;
-#pragma unroll 4
-      for (int r = 0; r < R; ++r) {
-        const double v = sc2[(size_t)tid * R + r];
-        b += v;
-        nb += v * v;
-      }
-      k2[tid] = b / R;
-      n2[tid] = sqrt(nb);
-    }
-    __syncthreads();
-    // fastAlignUsingVkey: thread = shift, first minimal shift wins
-    double nv = 1e300;
-    int ns = 0x7fffffff;
-    if (tid < S) {
-      double nn = 0;
-#pragma unroll 4
-      for (int s = 0; s < S; ++s) {
-        int j = s - tid;
-        j = j < 0 ? j + S : j;
-        const double d = k1[s] - k2[j];
-        nn += d * d;
-      }
-      nv = sqrt(nn);
-      ns = tid;
-      if (!(nv < 10000000)) {  // "cur_diff_norm < min" never true: shift 0 stays
-        nv = 1e300;
-        ns = 0x7fffffff;
-      }
-    }
-    block_argmin(nv, ns, sv, si);
-    const int argmin_vkey = ns == 0x7fffffff ? 0 : ns;
-    // column-shift search: the 2 radius + 1 shifts around it, ascending shift value = thread order
-    double dv = 1e300;
-    int ds = 0x7fffffff;
-    if (spread_shifts) {
-      // every (shift slot, column) term by all threads; slot i holds shift argmin - radius + i (mod S)
-      for (int p = tid; p < n_shift * S; p += SC_BLOCK) {
-        const int slot = p / S, col = p - slot * S;
-        int sh = argmin_vkey - P.radius + slot;
-        sh = sh < 0 ? sh + S : (sh >= S ? sh - S : sh);
-        int j = col - sh;
-        j = j < 0 ? j + S : j;
-        const double* a = sc1 + (size_t)col * R;
-        const double* b = sc2 + (size_t)j * R;
-        double dot = 0;
-#pragma unroll 4
-        for (int r = 0; r < R; ++r) dot += a[r] * b[r];
-        const double na = n1[col], nb2 = n2[j];
-        term[p] = (na == 0 || nb2 == 0) ? 1e300 : dot / (na * nb2);  // 1e300: the column is skipped
-      }
-      __syncthreads();
-      if (tid < S) {
-        int delta = tid - argmin_vkey;
-        delta = delta < 0 ? delta + S : delta;
-        const bool in = delta <= P.radius || S - delta <= P.radius;
-        if (in) {
-          const int slot = delta <= P.radius ? P.radius + delta : P.radius - (S - delta);
-          int n_eff = 0;
-          double sum = 0;
-#pragma unroll 4
-          for (int col = 0; col < S; ++col) {
-            const double t = term[slot * S + col];
-            if (t == 1e300) continue;
-            sum = sum + t;
-            n_eff = n_eff + 1;
-          }
-          const double d = 1.0 - sum / n_eff;
-          if (d < 10000000) {  // NaN (no effective column) never wins, like "cur < min"
-            dv = d;
-            ds = tid;
-          }
-        }
-      }
-    } else if (tid < S) {
-      // is shift `tid` in the search space {argmin + ii mod S, |ii| <= radius}?
-      int delta = tid - argmin_vkey;
-      delta = delta < 0 ? delta + S : delta;
-      const bool in = delta <= P.radius || S - delta <= P.radius;
-      if (in) {
-        int n_eff = 0;
-        double sum = 0;
-        for (int col = 0; col < S; ++col) {
-          int j = col - tid;
-          j = j < 0 ? j + S : j;
-          const double* a = sc1 + (size_t)col * R;
-          const double* b = sc2 + (size_t)j * R;
-          double na = 0, nb2 = 0, dot = 0;
-          for (int r = 0; r < R; ++r) {
-            na += a[r] * a[r];
-            nb2 += b[r] * b[r];
-            dot += a[r] * b[r];
-          }
-          na = sqrt(na);
-          nb2 = sqrt(nb2);
-          if (na == 0 || nb2 == 0) continue;
-          sum = sum + dot / (na * nb2);
-          n_eff = n_eff + 1;
-        }
-        const double d = 1.0 - sum / n_eff;
-        if (d < 10000000) {  // NaN (no effective column) never wins, like "cur < min"
-          dv = d;
-          ds = tid;
-        }
-      }
-    }
-    block_argmin(dv, ds, sv, si);
-    const int argmin_shift = ds == 0x7fffffff ? 0 : ds;
-    const double min_sc = ds == 0x7fffffff ? 10000000 : dv;
-    const double dx = pos[2 * (size_t)ci] - pos[2 * (size_t)node], dy = pos[2 * (size_t)ci + 1] - pos[2 * (size_t)node + 1];
-    double t_err = sqrt(dx * dx + dy * dy) - P.odom_eps;
-    t_err = (t_err > 0.0 ? t_err : 0.0) / (dist[ci] - dist[node]);
-    const double odom_dist = 1 - exp(-(t_err * t_err) / (2 * P.assumed_drift * P.assumed_drift));
-    const double cd = min_sc + odom_dist * R * P.odom_weight;
-    if (tid == 0) {
-      rec->cd = cd;
-      rec->shift = argmin_shift;
-      rec->idx = ci;
-    }
+  int argmin_shift;
+  double min_sc;
+  sc_descriptor_distance(P, desc + (size_t)node * R * S, desc + (size_t)ci * R * S, staged, spread_shifts, argmin_shift, min_sc);
+  const double odom_dist = sc_odom_term(P, pos[2 * (size_t)node], pos[2 * (size_t)node + 1], dist[node], pos[2 * (size_t)ci], pos[2 * (size_t)ci + 1], dist[ci]);
+  const double cd = min_sc + odom_dist * R * P.odom_weight;
+  if (tid == 0) {
+    rec->cd = cd;
+    rec->shift = argmin_shift;
+    rec->idx = ci;
   }
 }
 
@@ -451,24 +264,8 @@ __global__ __launch_bounds__(64) void k_sc_pick(ScParams P, int n_queries, int n
     }
   }
   loop_id[q] = min_d < P.dist_thresh ? nn_idx : -1;
-  yaw[q] = (float)((float)(nn_align * (360.0 / (double)P.S)) * M_PI / 180.0);
+  yaw[q] = sc_shift_yaw(nn_align, P.S);
   if (min_dist_out) min_dist_out[q] = min_d;
-}
-
-ScParams to_dev(const randt_sc_params* p) {
-  ScParams P;
-  P.R = p->num_ring;
-  P.S = p->num_sector;
-  P.exclude_recent = p->num_exclude_recent;
-  P.n_cand = p->num_candidates;
-  P.radius = (int)round(0.5 * p->search_ratio * p->num_sector);
-  P.max_radius = p->max_radius;
-  P.dist_thresh = p->dist_thresh;
-  P.assumed_drift = p->assumed_drift;
-  P.odom_eps = p->odom_eps;
-  P.odom_weight = p->odom_weight;
-  P.intensity_factor = p->intensity_factor;
-  return P;
 }
 
 }  // namespace

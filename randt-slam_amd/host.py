@@ -719,6 +719,19 @@ def sc_detect_batch(ctx, sp, desc, ring_keys, pos, dist, query_ids, loop_id, yaw
                "randt_sc_detect_batch_dev")
 
 
+def sc_query_batch(ctx, sp, desc, ring_keys, pos, dist, q_desc, q_ring_keys, q_pos, q_dist, loop_id, yaw, min_dist=None,
+                   cand_id=None, cand_yaw=None, cand_dist=None):
+    """randt_sc_query_batch_dev: place recognition for scans that are not database nodes.  Query q (q_desc[q], q_ring_keys[q])
+    searches all of desc / ring_keys; q_pos / q_dist None: no odometry term (pos / dist may then be None too).  cand_*:
+    (n_queries, num_candidates) device tensors, each optional."""
+    n_db = int(desc.shape[0]) if desc is not None else 0
+    nq = int(loop_id.shape[0])
+    ctx._check(ctx._lib.randt_sc_query_batch_dev(ctx._h, C.byref(sp), _dptr(desc), _dptr(ring_keys), _dptr(pos), _dptr(dist), n_db,
+                                                 _dptr(q_desc), _dptr(q_ring_keys), _dptr(q_pos), _dptr(q_dist), nq, _dptr(loop_id),
+                                                 _dptr(yaw), _dptr(min_dist), _dptr(cand_id), _dptr(cand_yaw), _dptr(cand_dist)),
+               "randt_sc_query_batch_dev")
+
+
 class ScDatabase:
     """SCManager's state on the device (randt_sc_db_*): append keyframe scans, query loop closures."""
 
@@ -746,6 +759,35 @@ class ScDatabase:
         lid, yaw, md = C.c_int(-1), C.c_float(0), C.c_double(0)
         self._ctx._check(self._ctx._lib.randt_sc_db_detect(self._h, int(node_id), C.byref(lid), C.byref(yaw), C.byref(md)), "randt_sc_db_detect")
         return lid.value, yaw.value, md.value
+
+    def query(self, points, odom_position=None, traversed_distance=None, intensity_index=None):
+        """randt_sc_db_query: a host scan that is NOT a node, against every node; the database stays as it is.  The odometry
+        prior is used only when both odom_position and traversed_distance are given.  Returns (loop_id or -1, yaw_diff_rad,
+        min_dist, cand_id, cand_yaw, cand_dist), the last three numpy arrays of num_candidates entries in rank order."""
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        n, stride = pts.shape
+        ioff = (3 if stride == 4 else 4) if intensity_index is None else intensity_index
+        prior = odom_position is not None and traversed_distance is not None
+        pos = np.ascontiguousarray(odom_position, dtype=np.float64) if prior else None
+        td = C.c_double(float(traversed_distance)) if prior else None
+        k = max(1, int(self.sp.num_candidates))
+        cid, cyaw, cd = np.full(k, -1, dtype=np.int32), np.zeros(k, dtype=np.float32), np.zeros(k)
+        lid, yaw, md = C.c_int(-1), C.c_float(0), C.c_double(0)
+        self._ctx._check(self._ctx._lib.randt_sc_db_query(self._h, pts.ctypes.data, n, stride, ioff, pos.ctypes.data if prior else None,
+                                                         C.byref(td) if prior else None, C.byref(lid), C.byref(yaw), C.byref(md),
+                                                         cid.ctypes.data, cyaw.ctypes.data, cd.ctypes.data), "randt_sc_db_query")
+        return lid.value, yaw.value, md.value, cid, cyaw, cd
+
+    def append_node(self, desc, ring_key, sector_key, odom_position, traversed_distance):
+        """randt_sc_db_append_node: stores a node from what download() returns, plus its odometry.  Returns the node id."""
+        d = np.ascontiguousarray(desc, dtype=np.float64)
+        rk, sk = np.ascontiguousarray(ring_key, dtype=np.float64), np.ascontiguousarray(sector_key, dtype=np.float64)
+        assert d.shape == (self.sp.num_sector, self.sp.num_ring) and rk.shape == (self.sp.num_ring,) and sk.shape == (self.sp.num_sector,)
+        pos = np.ascontiguousarray(odom_position, dtype=np.float64)
+        node = C.c_int(-1)
+        self._ctx._check(self._ctx._lib.randt_sc_db_append_node(self._h, d.ctypes.data, rk.ctypes.data, sk.ctypes.data, pos.ctypes.data,
+                                                               float(traversed_distance), C.byref(node)), "randt_sc_db_append_node")
+        return node.value
 
     def download(self, node_id):
         d = np.zeros((self.sp.num_sector, self.sp.num_ring))

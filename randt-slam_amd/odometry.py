@@ -168,6 +168,20 @@ class HipBackend:
         lid, yaw, _ = self._sc.detect(node_id)
         return lid, float(yaw)
 
+    def sc_query(self, points, pos=None, dist=None):
+        """a scan that is not a node against the whole database (which stays as it is); the odometry prior only with both pos
+        and dist.  Returns (loop_id, yaw, min_dist, cand_id, cand_yaw, cand_dist), the last three in rank order."""
+        pts = points.cpu().numpy() if hasattr(points, "data_ptr") else points
+        lid, yaw, md, cid, cyaw, cd = self._sc.query(pts, pos, dist)
+        return lid, float(yaw), float(md), cid, cyaw, cd
+
+    def sc_dist_thresh(self):
+        return float(self._sc.sp.dist_thresh)
+
+    def sc_append_node(self, desc, ring_key, sector_key, pos, dist):
+        """a node from its stored descriptor and keys (ScDatabase.download) instead of its scan"""
+        return self._sc.append_node(desc, ring_key, sector_key, pos, dist)
+
     def pose_graph_optimize(self, x, ia, ib, meas, sqi, max_update_index, params_kwargs):
         return host.pose_graph_optimize(self.ctx, x, ia, ib, meas, sqi, max_update_index, host.pg_params(**params_kwargs))
 

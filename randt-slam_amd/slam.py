@@ -136,6 +136,40 @@ class Slam(Odometry):
             added += self._close_loop(q, lid, sub_i, est, cs)                                           # :340-347
         return added
 
+    # ---- place recognition for a scan that is not part of the session (no counterpart in the reference) ----------
+    def relocalize(self, points, max_candidates=None):
+        """Where in the map was this scan taken?  For a restart, a tracking loss, or a scan of another session: the scan is
+        queried against the WHOLE Scan Context database without an odometry prior (it has none), every candidate below
+        dist_thresh whose submap is finished is refined exactly like a loop-closure candidate (:333-339: the same guess, the
+        same registration against the submap, the same CS divergence), and the candidate with the smallest divergence below
+        loop_closure_max_cs_divergence wins.  Neither the graph nor the database changes.
+        points: (N, stride) scan as process_scan takes it; max_candidates: at most this many ranks are refined (None: all).
+        Returns None, or a dict: pose (global pose4 of the scan), node (the candidate), submap, cs_divergence, sc_distance."""
+        if not hasattr(self.b, "sc_query"):
+            raise NotImplementedError("relocalize needs a backend with sc_query (odometry.HipBackend)")
+        if self.loop_search != "scan_context":
+            raise ValueError("relocalize needs loop_search='scan_context': there is no Scan Context database in this session")
+        scan = self.b.build_scan(points)
+        try:
+            _, _, _, cand_id, cand_yaw, cand_dist = self.b.sc_query(points)
+            n = len(cand_id) if max_candidates is None else min(len(cand_id), int(max_candidates))
+            best = None
+            for lid, yaw, dist in zip(cand_id[:n].tolist(), cand_yaw[:n].tolist(), cand_dist[:n].tolist()):
+                if lid < 0 or not dist < self.b.sc_dist_thresh():
+                    continue
+                sub_i = self.submap_idzs[lid]
+                if sub_i not in self.submaps:                  # the candidate's submap is still being built
+                    continue
+                root = self.nodes[self.root_nodes[sub_i]]
+                guess = _se2_mul4(_se2_mul4(_se2_inv4(root), self.nodes[lid]), _pose4(-yaw, 0.0, 0.0))   # as _scan_context_candidate
+                est, _cost = self.b.register_pair(self.submaps[sub_i], scan, self.loop_mp, guess)
+                cs = float(self.b.cs_divergence(self.submaps[sub_i], scan, est))
+                if cs < self.max_cs and (best is None or cs < best["cs_divergence"]):
+                    best = dict(pose=_se2_mul4(root, est), node=lid, submap=sub_i, cs_divergence=cs, sc_distance=dist)
+            return best
+        finally:
+            self.b.release_scan(scan)
+
     # ---- LocalFuser::detectLoopClosures, the branch without Scan Context (:351-412), quirks included -------
     def _covariance_candidates(self, q):
         """The candidates of query node q: per finished submap within the gate its closest node, in std::map order, as
